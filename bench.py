@@ -7,9 +7,14 @@ One "step" = one attack_rd.attack_ iteration over the per-GPU batch: L-inf box
 + input clamp, per-image branch (loss_i > -noise: input loss only, attack_rd.py:334-338), g_a + g_s forward,
 loss, g_s + g_a input-gradient backward for the images in the network branch (compacted sub-batch), Adam
 on the noise (attack_rd.py:506-559) — every kernel on HIP, inputs resident in HBM.  The line carries the
-branch census of the timed steps and (N = 1, hyperprior) of one whole 1001-step run with its wall time.
+branch census of the timed steps.
 
-    python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the line.  ``--dump-outputs DIR`` also writes what the
+last timed step left (the noise and its Adam state, per-image loss and branch) as DIR/<name>.npy.  ``--full`` adds
+everything that takes runs of its own: the per-kernel profiling pass and roofline, (N = 1, hyperprior) one whole
+1001-step run with its wall time and branch census, ``--mixed``, and the CPU baseline.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU, weak scaling)
 
 Images shard across GPUs (each rank attacks its own images; no collective on
@@ -148,6 +153,26 @@ _PREC_NAME = {0: "fp32", 1: "bf16", 2: "x6", 3: "bf16 (fp32 activations)"}
 
 def _peak(prec):
     return {1: BF16_MFMA_PEAK_TFLOPS, 2: X6_PEAK_TFLOPS, 3: BF16_MFMA_PEAK_TFLOPS}.get(prec, FP32_MFMA_PEAK_TFLOPS)
+
+
+DUMP_MAX_ELEMS = 4 << 20   # per array: 16 MB of float32, so a dump of three sampled tensors stays under 64 MB
+
+
+def _dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy (float32; float64 stays float64).  An array of more than DUMP_MAX_ELEMS
+    elements is written as a fixed sample: its flattened elements at DUMP_MAX_ELEMS indices drawn once from a
+    generator seeded by the array's size alone, so two builds run with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(n)
+            idx = torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def _dist_env():
@@ -313,32 +338,41 @@ def bench_finetune(args):
     g0 = dict(A.GRAPH_STATS)
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
-        adv_step(net, tr, opt, aux, xs[i], fargs, group, world)
+        last = adv_step(net, tr, opt, aux, xs[i], fargs, group, world)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last outer step returned (its losses and adversarial batch) and the weights it left
+        losses, batch_adv = last
+        arrays = {k: v for k, v in losses.items() if torch.is_tensor(v) or isinstance(v, float)}
+        arrays["batch_adv"] = batch_adv
+        arrays["params"] = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+        _dump_outputs(args.dump_outputs, arrays)
     coll, D.COLL_HOOK = D.COLL_HOOK, None
     # all-reduce time per outer step (HIP events around each collective on the issuing stream)
     coll_ms = {k: sum(a.elapsed_time(b) for a, b in v) / args.steps for k, v in (coll or {}).items()}
     replays = A.GRAPH_STATS["replays"] - g0["replays"]
     captures = A.GRAPH_STATS["captures"] - g0["captures"]
-    # Per-kernel times: the timed outer steps replay the inner attack's network step as a HIP graph (one launch per
-    # inner step; its kernels carry no events), so ONE more outer step runs right after them with the graph off and
-    # every tagged launch bracketed by HIP events: per-launch times, launch counts and the launch table of a whole
-    # outer step (the roofline and the PMC stamps refer to these launches, which run the same kernels on the same
-    # shapes as the replays).
-    graph_on, A.ATTACK_GRAPH = A.ATTACK_GRAPH, False
-    K.EVENT_HOOK = {}
-    K.FLOPS_HOOK = {}
-    K.PREC_HOOK = {}
-    K.LAUNCH_HOOK = {}
-    adv_step(net, tr, opt, aux, xs[args.warmup], fargs, group, world)
-    torch.cuda.synchronize()
-    A.ATTACK_GRAPH = graph_on
-    hook, K.EVENT_HOOK = K.EVENT_HOOK, None
-    table = _launch_table(K.LAUNCH_HOOK, rank)
-    K.LAUNCH_HOOK = None
+    hook, table = {}, {}
+    if args.full:
+        # Per-kernel times: the timed outer steps replay the inner attack's network step as a HIP graph (one launch
+        # per inner step; its kernels carry no events), so ONE more outer step runs right after them with the graph
+        # off and every tagged launch bracketed by HIP events: per-launch times, launch counts and the launch table
+        # of a whole outer step (the roofline and the PMC stamps refer to these launches, which run the same kernels
+        # on the same shapes as the replays).
+        graph_on, A.ATTACK_GRAPH = A.ATTACK_GRAPH, False
+        K.EVENT_HOOK = {}
+        K.FLOPS_HOOK = {}
+        K.PREC_HOOK = {}
+        K.LAUNCH_HOOK = {}
+        adv_step(net, tr, opt, aux, xs[args.warmup], fargs, group, world)
+        torch.cuda.synchronize()
+        A.ATTACK_GRAPH = graph_on
+        hook, K.EVENT_HOOK = K.EVENT_HOOK, None
+        table = _launch_table(K.LAUNCH_HOOK, rank)
+        K.LAUNCH_HOOK = None
     ranks = _rank_stats(dist, dev, el, B * inner * args.steps, world, extra=coll_ms.get("grad", 0.0) if dist else None)
     if dist:
         t = torch.tensor([el], device=dev, dtype=torch.float64)
@@ -348,7 +382,7 @@ def bench_finetune(args):
     flops_img = {t: (K.FLOPS_HOOK[t] if t in K.FLOPS_HOOK else layer_flops(t, N, M, H, W, 1)) for t in hook}
     tot_ms, tot_fl = _kernel_table(hook, flops_img)   # one eager outer step
     est_ms = dict(tot_ms)
-    dom = max(est_ms, key=est_ms.get)
+    dom = max(est_ms, key=est_ms.get) if est_ms else None
     wg = [t for t in tot_ms if t.endswith(".wgrad")]
     wdom = max(wg, key=tot_ms.get) if wg else None
 
@@ -383,15 +417,19 @@ def bench_finetune(args):
             "distributed": dict(ranks, **({"allreduce_ms_per_outer_step": {k: round(v, 4) for k, v in coll_ms.items()},
                                            "rank_extra_is": "flat-gradient all-reduce ms per outer step"}
                                           if dist else {})),
-            "roofline": roof(dom), "wgrad_roofline": roof(wdom),
-            "per_kernel_ms_total_per_outer_step": {k: round(v, 3) for k, v in sorted(est_ms.items())},
             "attack_graph": {"captures_per_outer_step": round(captures / args.steps, 3),
                              "replays_per_outer_step": round(replays / args.steps, 3),
-                             "note": "timed steps replay the inner network step as a HIP graph; per-kernel times, "
-                                     "roofline and launch table from one eager outer step run after them"},
-            "cpu_baseline": (None if world > 1 or args.no_cpu_baseline else
-                             cpu_baseline_finetune(q, metric, lmbda, B, H, W, inner)),
+                             "note": "timed steps replay the inner network step as a HIP graph"},
         }
+        if args.full:
+            out["attack_graph"]["note"] += ("; per-kernel times, roofline and launch table from one eager outer "
+                                            "step run after them")
+            out.update({
+                "roofline": roof(dom), "wgrad_roofline": roof(wdom),
+                "per_kernel_ms_total_per_outer_step": {k: round(v, 3) for k, v in sorted(est_ms.items())},
+                "cpu_baseline": (None if world > 1 or args.no_cpu_baseline else
+                                 cpu_baseline_finetune(q, metric, lmbda, B, H, W, inner)),
+            })
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
@@ -414,15 +452,21 @@ def main():
                     help="BASELINE.json configs[k-1] per-GPU shard: 2 hyper q3 fp32 (default), 3 cheng2020 q6, "
                          "4 train.py --adv fine-tune outer steps (8 x 256^2 per GPU, 300 inner steps, RCCL grad "
                          "all-reduce), 5 targeted ROI hyper q3 2048x2048 bf16")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-kernel profiling pass (roofline, "
+                         "launch table), the whole 1001-step run (--full-run), --mixed and the CPU baseline")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one left as DIR/<name>.npy (rank 0; float32, a "
+                         "fixed seeded sample of the large arrays, under 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--mixed", type=float, default=None, metavar="SCALE",
-                    help="also time one whole 1001-step run with g_a's last weight scaled by SCALE (40: O(1) latents "
+                    help="with --full: also time one whole 1001-step run with g_a's last weight scaled by SCALE (40: O(1) latents "
                          "as a trained codec has, so the run hovers at the -noise budget and both branches occur; "
                          "make_golden.py TRAJ100) and report its branch census, rate and host branch-read cost "
                          "next to the (unchanged, all-network-branch) headline")
     ap.add_argument("--full-run", dest="full_run", type=int, default=None,
-                    help="1: also run the whole 1001-step loop once (wall time + branch census of the full run); "
+                    help="with --full, 1: also run the whole 1001-step loop once (wall time + branch census of the full run); "
                          "default 1 for the hyperprior configs at N = 1, 0 for cheng2020 (~7 min)")
     args = ap.parse_args()
 
@@ -462,12 +506,11 @@ def main():
 
     from imagecompression_adversarial_amd import attack as A
     from imagecompression_adversarial_amd import codec as models
-    from imagecompression_adversarial_amd import hip_ops as K
     from imagecompression_adversarial_amd.attack import AttackLoop
     # the timed steps run the product path: the whole-batch network step replayed as a HIP graph (attack.py; also
-    # for the ROI attack), no timing hooks.  ICA_BENCH_GRAPH=0 times them eager (A/B).  Per-kernel times, the
-    # roofline and the launch table come from a profiling pass right after the timed region: the same number of
-    # eager steps with every tagged launch bracketed by HIP events.
+    # for the ROI attack), no timing hooks.  ICA_BENCH_GRAPH=0 times them eager (A/B).  With --full, per-kernel
+    # times, the roofline and the launch table come from a profiling pass right after the timed region: the same
+    # number of eager steps with every tagged launch bracketed by HIP events.
     A.ATTACK_GRAPH = A.ATTACK_GRAPH and os.environ.get("ICA_BENCH_GRAPH", "1") != "0"
     from imagecompression_adversarial_amd.engine import CodecKernels
     from imagecompression_adversarial_amd.engine_cheng import ChengKernels
@@ -507,6 +550,64 @@ def main():
     el = time.perf_counter() - t0
     exp_steps = loop.expensive_image_steps() - exp0   # image-steps of the timed window that ran the network
     graph_replays = loop.graph_replays - rep0
+    if args.dump_outputs and rank == 0:
+        # the state the last timed step left: the perturbation and its Adam moments, that step's per-image input
+        # loss and branch (1 = input-loss branch)
+        _dump_outputs(args.dump_outputs, {"noise": loop.noise, "adam_m": loop.m, "adam_v": loop.v,
+                                          "loss_i": loop.loss_i, "branch": loop.branch})
+    ranks = _rank_stats(dist, dev, el, B * args.steps, world)
+    if dist:
+        t = torch.tensor([el], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        el = float(t.item())
+    ms_step = el / args.steps * 1e3
+    value = B * world * args.steps / el
+    metric = METRIC if model == "hyper" else \
+        "attack-step·images/sec, Cheng2020-anchor q6 768×512 (configs[2] per-GPU shard)"
+    if roi_mode:
+        metric = "attack-step·images/sec, targeted ROI attack Balle2018-hyper 2048×2048 bf16 (configs[4] per-GPU shard)"
+    name = "hyper" if model == "hyper" else "cheng2020"
+    out = {
+        "metric": metric, "value": round(value, 3), "unit": "attack-step·images/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"bf16": ("bf16 operands, f32 accumulate" if model == "hyper" else
+                           "bf16 operands over f32 activations on the k3 conv_downs, f32 accumulate"),
+                  "x6": "f32 (fp32-accurate: exact 3-way bf16 operand splits, 6 MFMA products, f32 accumulate)",
+                  }.get(args.precision, "f32"),
+        "data": "synthetic (torch.rand images, seeded CompressAI-init weights)",
+        "config": {"workload": (f"attack_rd -m {name} -q {args.quality} -att_metric L2 -noise 1e-4"
+                                + (f" -t <target> --mask_loc {W // 4} {3 * W // 4} {H // 4} {3 * H // 4}"
+                                   if roi_mode else "")
+                                + f", {B} images/GPU of {W}x{H}, steps of the 1001-step loop, "
+                                  f"{args.precision} conv operands"),
+                   "per_gpu_batch": B, "global_batch": B * world, "height": H, "width": W,
+                   "parallelism": f"image-shard x{world} (no data-path collective)"},
+        "branch_census": {"expensive_image_steps": exp_steps, "image_steps": B * args.steps,
+                          "expensive_frac": round(exp_steps / (B * args.steps), 4)},
+        "timing": {"timed_steps": ("network step replayed as a HIP graph (product default)" if graph_replays
+                                   else "eager"),
+                   "graph_replays": graph_replays},
+        "distributed": ranks,
+    }
+    if args.full:
+        extra = _full_report(args, loop, kern, sd, im_s, roi_kw, roi_mode, model, world, rank, ms_step)
+        out["timing"].update(extra.pop("timing"))
+        out.update(extra)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist:
+        dist.destroy_process_group()
+
+
+def _full_report(args, loop, kern, sd, im_s, roi_kw, roi_mode, model, world, rank, ms_step):
+    """--full: what the headline figure does not need, each from a run of its own after the timed steps -- the
+    profiling pass (per-kernel times, roofline, launch table), the whole 1001-step run, --mixed, the CPU baseline."""
+    from imagecompression_adversarial_amd import hip_ops as K
+    from imagecompression_adversarial_amd.attack import AttackLoop
+    from imagecompression_adversarial_amd.engine import CodecKernels
+    B, _, H, W = im_s.shape
+    N, M = kern.N, kern.M
     # profiling pass: as many eager steps, every tagged launch timed by HIP events on its stream
     graph_ok, loop.graph_ok = loop.graph_ok, False
     K.EVENT_HOOK = {}
@@ -522,11 +623,6 @@ def main():
     hook, K.EVENT_HOOK = K.EVENT_HOOK, None
     table = _launch_table(K.LAUNCH_HOOK, rank)
     K.LAUNCH_HOOK = None
-    ranks = _rank_stats(dist, dev, el, B * args.steps, world)
-    if dist:
-        t = torch.tensor([el], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        el = float(t.item())
 
     # per-kernel durations (HIP events on the launch stream) and algorithmic FLOPs of every launch: a launch
     # covers the images of its (compacted) batch, so the FLOPs are per-image FLOPs x the launch's images
@@ -559,8 +655,6 @@ def main():
     # network FLOPs per timed step, weighted by the branches actually taken (a cheap-branch
     # image-step runs no network and counts 0): the launches only covered the expensive images
     total_flops = sum(tot_fl.values()) / args.steps
-    ms_step = el / args.steps * 1e3
-    value = B * world * args.steps / el
 
     # the whole 1001-step loop once (N == 1): wall time, img-step/s and the branch census of the full run
     full = None
@@ -600,60 +694,31 @@ def main():
                  "ms_per_step": round(fe / 1001 * 1e3, 3)}
         del loop3, kern2
 
+    cpu = None
     if rank == 0:
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             # cheng2020 and the 2048x2048 tiles take seconds per image-step on the CPU: their batch variant is 4 / 2
             # images, not the GPU's batch (the sample stays at ~1 min of CPU work)
             cpu = cpu_baseline(H, W, args.quality, args.cpu_seconds, model,
                                big_batch=4 if model == "cheng2020" else (2 if roi_mode else 32))
-        metric = METRIC if model == "hyper" else \
-            "attack-step·images/sec, Cheng2020-anchor q6 768×512 (configs[2] per-GPU shard)"
-        if roi_mode:
-            metric = "attack-step·images/sec, targeted ROI attack Balle2018-hyper 2048×2048 bf16 (configs[4] per-GPU shard)"
-        name = "hyper" if model == "hyper" else "cheng2020"
-        out = {
-            "metric": metric, "value": round(value, 3), "unit": "attack-step·images/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"bf16": ("bf16 operands, f32 accumulate" if model == "hyper" else
-                               "bf16 operands over f32 activations on the k3 conv_downs, f32 accumulate"),
-                      "x6": "f32 (fp32-accurate: exact 3-way bf16 operand splits, 6 MFMA products, f32 accumulate)",
-                      }.get(args.precision, "f32"),
-            "data": "synthetic (torch.rand images, seeded CompressAI-init weights)",
-            "config": {"workload": (f"attack_rd -m {name} -q {args.quality} -att_metric L2 -noise 1e-4"
-                                    + (f" -t <target> --mask_loc {W // 4} {3 * W // 4} {H // 4} {3 * H // 4}"
-                                       if roi_mode else "")
-                                    + f", {B} images/GPU of {W}x{H}, steps of the 1001-step loop, "
-                                      f"{args.precision} conv operands"),
-                       "per_gpu_batch": B, "global_batch": B * world, "height": H, "width": W,
-                       "parallelism": f"image-shard x{world} (no data-path collective)"},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2),
-                         "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_note,
-                         "launch_ms": round(dom_ms, 4), "flops_per_launch": dom_flops},
-            "branch_census": {"expensive_image_steps": exp_steps, "image_steps": B * args.steps,
-                              "expensive_frac": round(exp_steps / (B * args.steps), 4)},
-            "timing": {"timed_steps": ("network step replayed as a HIP graph (product default)" if graph_replays
-                                       else "eager"),
-                       "graph_replays": graph_replays,
-                       "per_kernel_source": f"profiling pass: {args.steps} eager steps right after the timed region, "
-                                            "every tagged launch bracketed by HIP events on its stream",
-                       "profiling_pass_expensive_image_steps": prof_exp},
-            "distributed": ranks,
-            "full_run": full,
-            "mixed_branch_run": mixed,
-            "step_gflop_per_image": round(total_flops / B / 1e9, 2),
-            "step_tflops": round(total_flops / (ms_step * 1e-3) / 1e12, 2),
-            "step_roofline_frac": round(total_flops / (ms_step * 1e-3) / 1e12 /
-                                        _peak({"bf16": 1, "x6": 2}.get(args.precision, 0)),
-                                        4),
-            "per_kernel_ms": {k: round(v, 4) for k, v in sorted(per_tag.items())},
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(out), flush=True)
-    if dist:
-        dist.destroy_process_group()
+    return {
+        "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 2),
+                     "peak": peak, "unit": "TFLOP/s",
+                     "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_note,
+                     "launch_ms": round(dom_ms, 4), "flops_per_launch": dom_flops},
+        "timing": {"per_kernel_source": f"profiling pass: {args.steps} eager steps right after the timed region, "
+                                        "every tagged launch bracketed by HIP events on its stream",
+                   "profiling_pass_expensive_image_steps": prof_exp},
+        "full_run": full,
+        "mixed_branch_run": mixed,
+        "step_gflop_per_image": round(total_flops / B / 1e9, 2),
+        "step_tflops": round(total_flops / (ms_step * 1e-3) / 1e12, 2),
+        "step_roofline_frac": round(total_flops / (ms_step * 1e-3) / 1e12 /
+                                    _peak({"bf16": 1, "x6": 2}.get(args.precision, 0)),
+                                    4),
+        "per_kernel_ms": {k: round(v, 4) for k, v in sorted(per_tag.items())},
+        "cpu_baseline": cpu,
+    }
 
 
 if __name__ == "__main__":
