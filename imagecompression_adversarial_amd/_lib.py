@@ -65,6 +65,11 @@ _SIGS = {
     "ica_roi_adam": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _p, _i, _i, _i, _i, _f, _f, _p, _p, _p],
     "ica_ifgsm_step": [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _i, _p],
     "ica_l1_partial": [_p, _p, _i, _i, _i, _p],
+    # C&W-style binary-search attack (ica_cw.hip)
+    "ica_cw_gate": [_p, _i, _f, _p, _p, _p, _p, _i, _p],
+    "ica_cw_adam": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p, _i, _p, _i, _p],
+    "ica_cw_round": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
+    "ica_cw_reset": [_p, _p, _p, _p, _i, _l, _p],
     "ica_gc_likelihood": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ica_eb_likelihood": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ica_pack_eb": [_p, _p, _p, _i, _p],

@@ -12,7 +12,7 @@ decompress() on libica_hip.
             sequential 64-bit rANS state), images of a batch on parallel host threads (ctypes drops the GIL).
   dequant   decoded symbols back into nChw4c latents on the GPU (ica_dequantize).
 
-The context models (mbt2018, cheng2020) need CompressAI's autoregressive decoder, which is not built.
+The context models (mbt2018, cheng2020) code through the autoregressive path of ar_coding.py (ica_ar.hip).
 """
 from __future__ import annotations
 

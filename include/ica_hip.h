@@ -20,6 +20,7 @@
  *   GDN / IGDN (fwd + bwd) .......................... utils/ops.py:58-97  (== compressai.layers.GDN)
  *   Low_bound / Up_bound (clamp + pass-through) ..... utils/ops.py:28-56
  *   attack step (box, clamp, L2 loss, branch, Adam)  attack_rd.py:496-559, attack_our :332-379
+ *   C&W-style search (gate, Adam, both bisections) . attack_cw.py:115-199, 238-259; attack_cw_fast.py:100-183, 222-243
  *   I-FGSM / MI-FGSM update + projection ........... attack_ifgsm.py:348-362, 405-419
  *   EntropyBottleneck / GaussianConditional lik. ... anchors/model.py:86-108, anchors/balle.py:31-55 (CompressAI)
  *   bpp ............................................. attack_rd.py:419, self_ensemble.py:222
@@ -330,6 +331,40 @@ int ica_clamp01(const float* x, float* y, long n, hipStream_t stream);
 int ica_sqdiff_partial(const float* a, const float* b, float* part, int B, long len, int clamp_a, hipStream_t stream);
 int ica_nc4_bound_to_nchw(const float* x4, float* out, int B, int H, int W, int clamp, hipStream_t stream);
 int ica_bound_bwd_nc4(const float* x4, const float* g, float* g4, int B, int H, int W, int clamp, hipStream_t stream);
+
+/* ---- C&W-style binary-search attack (ica_cw.hip) ---------------------------
+ * Replaces, per image of a batch and with the search state on the device:
+ *   attack_cw.py:115-140 (attack_cw: step loss and the gate on c), :142-199 (search_noise: the step loop with
+ *   torch.optim.Adam and the bisection on c), :238-259 (attack_: the outer search on the level);
+ *   attack_cw_fast.py:100-125, :127-183 (the width / residual rule that ends a level), :222-243.
+ * Per-image state, field-major (field f of image b at [f * B + b]), allocated by the caller on the device:
+ *   sd   double [6][B]   0 c_l, 1 c_r, 2 c, 3 level, 4 min, 5 max
+ *   lold float  [B]      loss_i_old
+ *   si   int    [5][B]   0 t (Adam steps of the current level), 1 round (rounds done in the level),
+ *                        2 levels (levels completed), 3 active, 4 reset
+ * Start of a run: c_l = 0, c_r = c = la, level = max = the start level, min = noise, lold = 0, si = 0 but active = 1.
+ * A step is ica_attack_prologue_ex + ica_reduce_rows (loss_i), g_a / g_s / ica_attack_loss (mode 0, part) and the
+ * network backward, then ica_cw_gate and ica_cw_adam; after every `steps` steps ica_cw_round and ica_cw_reset. */
+/* mse_o[b] = invN * sum part[b][0..nblk) (ica_reduce_rows' order); c_eff[b] = mse_o[b] > 1.1 * level[b] ? 0 : c[b];
+ * t[b] += 1.  Images with active[b] == 0: c_eff[b] = 0, mse_o[b] and t[b] unchanged. */
+int ica_cw_gate(const float* part, int nblk, float invN, const double* sd, int* si, float* mse_o, float* c_eff, int B,
+                hipStream_t stream);
+/* g = -2 fl(invN (im_s - im_in)) + c_eff[b] * gnet4 (the network's gradient of loss_o at unit weight), the [0, 1]
+ * (clamp_in) and +-eps pass-through gates, torch-Adam on noise / m / v with (bc2s, neg_step) = tab[t[b] - 1]
+ * (tab: ntab float pairs on the device).  Images with active[b] == 0 are left untouched.  im_in_out (optional):
+ * im_in of the active images.  Returns -2 unless H * W is a multiple of 4. */
+int ica_cw_adam(float* noise, const float* im_s, const float* gnet4, const float* c_eff, float* m, float* v,
+                float* im_in_out, int B, int H, int W, float eps, float invN, const float* tab, int ntab, const int* si,
+                int clamp_in, hipStream_t stream);
+/* End of a round for the active images: bisection on c (mse_o < 0.99 level: c_l = c, else c_r = c), end of the
+ * level (fast 0: after ssteps rounds; fast 1: attack_cw_fast's rule; either: after max_rounds rounds), the stop
+ * test and the bisection on the level with loss_i, active = 0 when the image is done.  reset[b] is rewritten for
+ * every image: 1 when it starts a new level.  *n_active = images still active.  cfg: HOST array {la, noise}. */
+int ica_cw_round(const float* loss_i, const float* mse_o, double* sd, float* lold, int* si, int* n_active, int B,
+                 int fast, int ssteps, int max_rounds, const double* cfg, hipStream_t stream);
+/* noise = m = v = 0 for the images with reset[b] (floats_per_image a multiple of 4).  The flag is not cleared
+ * here (every block of the image reads it); the next ica_cw_round rewrites it. */
+int ica_cw_reset(float* noise, float* m, float* v, const int* si, int B, long floats_per_image, hipStream_t stream);
 
 /* ---- MS-SSIM (ica_msssim.hip) ---------------------------------------------- */
 /* mode 0 = pytorch_msssim (valid, per-channel, relu), mode 1 = utils/torch_msssim (same-pad, global). */
