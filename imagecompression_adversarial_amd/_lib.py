@@ -47,8 +47,6 @@ _SIGS = {
     "ica_pack_up3_size": [_i],
     "ica_pack_up3": [_p, _p, _i, _p],
     "ica_conv_up3": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "ica_conv_down": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
-    "ica_conv_up": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "ica_elem_blocks_per_image": [],
     "ica_nchw_to_nc4": [_p, _p, _i, _i, _i, _i, _p],
     "ica_nc4_to_nchw": [_p, _p, _i, _i, _i, _i, _p],
@@ -136,7 +134,7 @@ class ConvArgs(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("x", "y", "wp", "bias", "gp", "beta", "save_x", "save_s", "in_x", "in_s",
                                             "save_t", "res", "mask")]
                 + [(n, C.c_int) for n in ("N", "Cin", "Hin", "Win", "Cout", "Hout", "Wout", "kind", "KS", "S", "epi",
-                                           "it", "fill_mode", "ps", "prec", "layout")])
+                                           "it", "fill_mode", "ps", "prec", "layout", "order")])
 
 
 class ArArgs(C.Structure):

@@ -2119,7 +2119,8 @@ static int pick_up(const ConvParams& p, int KS, int it, int epi, int fx, hipStre
 }
 
 // fp32-accurate bf16x6 operand kernels (ica_conv_x6.hip)
-int ica_conv_x6_dispatch(const ConvParams& p, int kind, int KS, int S, int it, int epi, int fx, hipStream_t st);
+int ica_conv_x6_dispatch(const ConvParams& p, int kind, int KS, int S, int it, int epi, int fx, int order,
+                         hipStream_t st);
 int ica_rgb5_bf16_dispatch(const ConvParams& p, int epi, hipStream_t st);
 int ica_pack_rgb5_planes(const float* w, void* dst, int O, int C, long so, long sc, int it, int planes, hipStream_t st);
 
@@ -2168,6 +2169,7 @@ typedef struct ica_conv_args {
   int kind, KS, S, epi, it, fill_mode, ps;
   int prec;   /* 0 fp32 operands, 1 bf16 operands (fp32 accumulate), 2 bf16x6 (fp32-accurate) */
   int layout; /* parity-split tensors: 1 = x, 2 = the output-layout tensors (ConvParams::pl) */
+  int order;  /* fragment order of wp (ORDER_*) */
 } ica_conv_args;
 
 // Channel tile (IT = number of 32-channel MFMA row tiles per wave) the conv
@@ -2406,27 +2408,6 @@ int ica_pack_gdn(const float* gamma, const float* beta, float* gp, float* beta_e
   return 0;
 }
 
-int ica_conv_down(const float* x, float* y, const float* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                  int Cout, int Hout, int Wout, int KS, int S, int epi, const float* gp, const float* beta,
-                  float* save_x, float* save_s, const float* in_x, const float* in_s, float* save_t,
-                  hipStream_t st) {
-  ConvParams p{x, y, wp, bias, gp, beta, save_x, save_s, in_x, in_s, N, Cin, Hin, Win, Cout, Hout, Wout, save_t};
-  const int it = ica_conv_it(Cout);
-  if (epi >= EPI_GDN && epi <= EPI_IGDN_BWD && Cout != it * 32) return -4;
-  const int fx = (save_x ? FX_RES : 0) | (save_t ? FX_T : 0);
-  return pick_down(p, KS, S, it, epi, fx, st);
-}
-
-int ica_conv_up(const float* x, float* y, const float* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                int Cout, int Hout, int Wout, int epi, const float* gp, const float* beta, float* save_x,
-                float* save_s, const float* in_x, const float* in_s, float* save_t, hipStream_t st) {
-  ConvParams p{x, y, wp, bias, gp, beta, save_x, save_s, in_x, in_s, N, Cin, Hin, Win, Cout, Hout, Wout, save_t};
-  const int it = ica_conv_it(Cout);
-  if (epi >= EPI_GDN && epi <= EPI_IGDN_BWD && Cout != it * 32) return -4;
-  const int fx = (save_x ? FX_RES : 0) | (save_t ? FX_T : 0);
-  return pick_up(p, 5, it, epi, fx, st);
-}
-
 int ica_conv_ex(const ica_conv_args* a, hipStream_t st) {
   ConvParams p{a->x,    a->y,    a->wp,   a->bias, a->gp,   a->beta, a->save_x, a->save_s, a->in_x, a->in_s,
                a->N,    a->Cin,  a->Hin,  a->Win,  a->Cout, a->Hout, a->Wout,   a->save_t, a->res,  a->mask,
@@ -2445,16 +2426,24 @@ int ica_conv_ex(const ica_conv_args* a, hipStream_t st) {
   if (a->epi == EPI_LRELU_BWD && !a->in_x) return -4;
   const int fx = ((a->res || a->save_x) ? FX_RES : 0) | (a->ps ? FX_PS : 0) | (a->fill_mode == 1 ? FX_MASK : 0) |
                  (a->fill_mode == 2 ? FX_UNSHUF : 0) | (a->save_t ? FX_T : 0);
+  // every route below reads one fragment order (down for kind 0, up for kind 1, the bf16 tap groups for a bf16
+  // conv_down with <= 4 input channels); a pack in any other order is refused, never read as something else
+  const int want = a->kind == 1 ? ORDER_UP : ORDER_DOWN;
   if (a->prec == 2) {
-    if (a->kind == 0 && a->KS == 3) return pick_x6o<3>(p, a->kind, a->KS, a->S, a->epi, it, fx, st);
-    return ica_conv_x6_dispatch(p, a->kind, a->KS, a->S, it, a->epi, fx, st);
+    if (a->kind == 0 && a->KS == 3)
+      return a->order == want ? pick_x6o<3>(p, a->kind, a->KS, a->S, a->epi, it, fx, st) : -4;
+    return ica_conv_x6_dispatch(p, a->kind, a->KS, a->S, it, a->epi, fx, a->order, st);
   }
   // bf16 operands over fp32 activations: the k3 conv_downs only, on the x6 pack's hi plane (cheng2020 bf16)
-  if (a->prec == 3) return pick_x6o<1>(p, a->kind, a->KS, a->S, a->epi, it, fx, st);
-  // bf16 RGB-side conv_down with the dense tap-row pack (hip_ops packs order 2 for exactly these layers)
-  if (a->prec == 1 && a->kind == 0 && a->KS == 5 && a->S == 2 && a->Cin <= 3 && a->Cout == 128 && it == 4 && fx == 0 &&
-      a->fill_mode == 0 && (a->epi == EPI_BIAS || a->epi == EPI_GDN || a->epi == EPI_IGDN_BWD))
+  if (a->prec == 3) return a->order == want ? pick_x6o<1>(p, a->kind, a->KS, a->S, a->epi, it, fx, st) : -4;
+  // bf16 RGB-side conv_down on the dense tap-row pack: conv_rgb5_bf16 or nothing
+  if (a->prec == 1 && a->order == ORDER_RGB5) {
+    if (a->kind != 0 || a->KS != 5 || a->S != 2 || it != 4 || fx != 0 || a->fill_mode != 0 ||
+        !(a->epi == EPI_BIAS || a->epi == EPI_GDN || a->epi == EPI_IGDN_BWD))
+      return -4;
     return ica_rgb5_bf16_dispatch(p, a->epi, st);
+  }
+  if (a->order != (a->prec == 1 && a->kind == 0 && a->Cin <= 4 ? ORDER_TG : want)) return -4;
   if (a->kind == 0) return pick_down(p, a->KS, a->S, it, a->epi, fx, st);
   if (a->kind == 1) return a->S == 2 ? pick_up(p, a->KS, it, a->epi, fx, st) : -6;
   return -6;

@@ -58,6 +58,9 @@ struct ConvParams {
                       // save_x / save_s, in_x / in_s, save_t, res); x6 k5 s2 kernels and the x6 conv_up3 only
 };
 enum { PL_IN = 1, PL_OUT = 2 };
+// fragment order of a packed weight (ica_conv_args.order; include/ica_hip.h ICA_ORDER_*): what a launch's kernel
+// reads.  ica_conv_ex checks it against the route it takes and never infers a layout from the launch's shape.
+enum { ORDER_DOWN = 0, ORDER_UP = 1, ORDER_RGB5 = 2, ORDER_TG = 3 };
 
 // v -> (hi, mid, lo) bf16 quads, each stage round-to-nearest-even on the residual (exact: hi + mid + lo == v)
 ICA_DEV void split3(f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {

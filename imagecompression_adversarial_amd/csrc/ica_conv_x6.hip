@@ -2498,8 +2498,13 @@ int ica_pack_rgb5_planes(const float* w, void* dst, int O, int C, long so, long 
 
 // x6 launches (ica_conv_ex with prec = 2): the k5 s2 conv (kind 0) and transposed conv (kind 1) layers of the
 // bmshj2018 transforms.  Returns -4 / -3 / -2 / -5 for shapes / epilogues without an x6 kernel: nothing falls back
-// here; hip_ops.x6_ok restates this coverage so that PackedConv keeps the fp32 pack for such layers.
-int ica_conv_x6_dispatch(const ConvParams& p, int kind, int KS, int S, int it, int epi, int fx, hipStream_t st) {
+// here.  order is the fragment order of p.wp: every route takes the one order its kernel reads (up for kind 1, down
+// for kind 0, the dense tap-row pack for the RGB-sized input) and returns -4 for any other, so a pack chosen by
+// hip_ops.x6_ok for a layer this dispatch does not cover is rejected, not misread.
+int ica_conv_x6_dispatch(const ConvParams& p, int kind, int KS, int S, int it, int epi, int fx, int order,
+                         hipStream_t st) {
+  const bool rgb = kind == 0 && KS == 5 && S == 2 && p.Cin <= 4;
+  if (order != (rgb ? ORDER_RGB5 : kind == 1 ? ORDER_UP : ORDER_DOWN)) return -4;
   if (kind == 1 && KS == 3 && S == 2) return pick_up3s2_x6(p, it, epi, fx, st);
   if (kind == 1 && KS == 1 && S == 2) {   // cheng2020's 1x1 stride-2 skips (no residual)
     if (epi != EPI_BIAS || fx != 0 || p.Cout % 32 != 0) return -4;

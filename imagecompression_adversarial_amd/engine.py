@@ -95,13 +95,12 @@ class Analysis:
         for i in range(3):   # layer i: level i -> level i + 1
             p = self.convs[i]
             h, sx, ss = K.conv_down(h, C, p.fwd, p.bias, self.N, 5, 2, K.EPI_GDN, self.gdns[i], save,
-                                    tag=f"{self.tag}.{2 * i}.fwd", prec=p.fwd_prec, it=p.it_fwd,
-                                    layout=_lay(lv, i, i + 1))
+                                    tag=f"{self.tag}.{2 * i}.fwd", layout=_lay(lv, i, i + 1))
             saved.append((sx, ss))
             C = self.N
         p = self.convs[3]
         y, _, _ = K.conv_down(h, self.N, p.fwd, p.bias, self.M, 5, 2, K.EPI_BIAS, tag=f"{self.tag}.6.fwd",
-                              prec=p.fwd_prec, layout=_lay(lv, 3, 4))
+                              layout=_lay(lv, 3, 4))
         return y, saved
 
     def backward(self, gy4, saved):
@@ -113,11 +112,10 @@ class Analysis:
         g, C = gy4, self.M
         for i in (3, 2, 1):
             g, _, _ = K.conv_up(g, C, self.convs[i].bwd, None, self.N, K.EPI_GDN_BWD, self.gdns[i - 1],
-                                saved=saved[i - 1], tag=f"{self.tag}.{2 * i}.dgrad", prec=self.convs[i].bwd_prec,
-                                it=self.convs[i].it_bwd, layout=_lay(lv, i + 1, i))
+                                saved=saved[i - 1], tag=f"{self.tag}.{2 * i}.dgrad", layout=_lay(lv, i + 1, i))
             C = self.N
         gx, _, _ = K.conv_up(g, self.N, self.convs[0].bwd, None, 3, K.EPI_BIAS, tag=f"{self.tag}.0.dgrad",
-                             prec=self.convs[0].bwd_prec, layout=_lay(lv, 1, 0))
+                             layout=_lay(lv, 1, 0))
         return gx
 
 
@@ -143,12 +141,11 @@ class Synthesis:
         for i in range(3):   # layer i: level 4 - i -> level 3 - i
             p = self.convs[i]
             h, sx, ss = K.conv_up(h, C, p.fwd, p.bias, self.N, K.EPI_IGDN, self.gdns[i], save,
-                                  tag=f"{self.tag}.{2 * i}.fwd", prec=p.fwd_prec, it=p.it_fwd,
-                                  layout=_lay(lv, 4 - i, 3 - i))
+                                  tag=f"{self.tag}.{2 * i}.fwd", layout=_lay(lv, 4 - i, 3 - i))
             saved.append((sx, ss))
             C = self.N
         p = self.convs[3]
-        xh, _, _ = K.conv_up(h, self.N, p.fwd, p.bias, 3, K.EPI_BIAS, tag=f"{self.tag}.6.fwd", prec=p.fwd_prec,
+        xh, _, _ = K.conv_up(h, self.N, p.fwd, p.bias, 3, K.EPI_BIAS, tag=f"{self.tag}.6.fwd",
                              layout=_lay(lv, 1, 0))
         return xh, saved
 
@@ -157,11 +154,10 @@ class Synthesis:
         g, C = gx4, 3
         for i in (3, 2, 1):   # level 3 - i -> level 4 - i
             g, _, _ = K.conv_down(g, C, self.convs[i].bwd, None, self.N, 5, 2, K.EPI_IGDN_BWD, self.gdns[i - 1],
-                                  saved=saved[i - 1], tag=f"{self.tag}.{2 * i}.dgrad", prec=self.convs[i].bwd_prec,
-                                  it=self.convs[i].it_bwd, layout=_lay(lv, 3 - i, 4 - i))
+                                  saved=saved[i - 1], tag=f"{self.tag}.{2 * i}.dgrad", layout=_lay(lv, 3 - i, 4 - i))
             C = self.N
         gy, _, _ = K.conv_down(g, self.N, self.convs[0].bwd, None, self.M, 5, 2, K.EPI_BIAS,
-                               tag=f"{self.tag}.0.dgrad", prec=self.convs[0].bwd_prec, layout=_lay(lv, 3, 4))
+                               tag=f"{self.tag}.0.dgrad", layout=_lay(lv, 3, 4))
         return gy
 
 
@@ -199,8 +195,8 @@ class HyperSynthesis:
 
     def forward(self, z4):
         p0, p1, p2 = self.convs
-        s, _, _ = K.conv_up(z4, self.N, p0.fwd, p0.bias, self.N, K.EPI_RELU, it=p0.it_fwd)
-        s, _, _ = K.conv_up(s, self.N, p1.fwd, p1.bias, self.N, K.EPI_RELU, it=p1.it_fwd)
+        s, _, _ = K.conv_up(z4, self.N, p0.fwd, p0.bias, self.N, K.EPI_RELU)
+        s, _, _ = K.conv_up(s, self.N, p1.fwd, p1.bias, self.N, K.EPI_RELU)
         s, _, _ = K.conv_down(s, self.N, p2.fwd, p2.bias, self.M, 3, 1, K.EPI_RELU)
         return s
 
@@ -246,8 +242,8 @@ class MbtHyperSynthesis:
 
     def forward(self, z4):
         p0, p1, p2 = self.convs
-        s, _, _ = K.conv_up(z4, self.N, p0.fwd, p0.bias, self.M, K.EPI_LRELU, it=p0.it_fwd)
-        s, _, _ = K.conv_up(s, self.M, p1.fwd, p1.bias, self.M3, K.EPI_LRELU, it=p1.it_fwd)
+        s, _, _ = K.conv_up(z4, self.N, p0.fwd, p0.bias, self.M, K.EPI_LRELU)
+        s, _, _ = K.conv_up(s, self.M, p1.fwd, p1.bias, self.M3, K.EPI_LRELU)
         s, _, _ = K.conv_down(s, self.M3, p2.fwd, p2.bias, self.out_channels, 3, 1, K.EPI_BIAS)
         return s
 

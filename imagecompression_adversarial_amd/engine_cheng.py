@@ -66,110 +66,88 @@ X6_IT = (4, 6)   # row tiles of the x6 k3 s1 conv_down instantiations (ica_conv.
 X6_IT_PS = (1, 4, 6)   # ... and of the subpel forwards (IT = 1: g_s.7's 16 rho rows, bias + PixelShuffle only)
 
 
-class Conv3:
-    """One Conv2d(k in {1,3,5}, stride s, pad k//2) layer, packed for its forward and its input gradient."""
-
-    def __init__(self, w, b, stride=1, fwd_only=False, mask=None, x6=False, b1=False):
-        """b1 (with x6): the X6O conv_down launches (k3 s1 forward / input gradient, k3 s2 forward) run bf16
-        operands over fp32 activations (hip_ops.PREC_B1: the x6 pack's hi plane); the stride-2 input gradients keep
-        x6 (cheng2020 --precision bf16)."""
-        w = w.detach()
-        self.p6 = K.PREC_B1 if b1 else K.PREC_X6
-        if mask is not None:
-            w = (w * mask.to(w.device)).contiguous()
-        self.Cout, self.Cin, self.KS = w.shape[0], w.shape[1], w.shape[-1]
-        self.S = stride
-        KK = self.KS * self.KS
-        self.it = _it(self.Cout)
-        cc = 4 if self.Cin <= 4 else 16
-        self.fwd = K.pack_conv(w, self.Cout, self.Cin, self.KS, self.Cin * KK, KK, K.ORDER_DOWN, cc, it=self.it)
-        self.bias = None if b is None else b.detach().contiguous()
-        self.bwd = None
-        self.it_b = _it(self.Cin)
-        if not fwd_only:
-            if stride == 1:   # dgrad = conv with the taps reversed, channels swapped
-                self.bwd = K.pack_conv(w, self.Cin, self.Cout, self.KS, KK, self.Cin * KK, K.ORDER_DOWN, 16,
-                                       flip=True, it=self.it_b)
-            else:             # dgrad = stride-2 transposed conv (conv_up, KS in {3, 1})
-                self.bwd = K.pack_conv(w, self.Cin, self.Cout, self.KS, KK, self.Cin * KK, K.ORDER_UP, 16,
-                                       it=self.it_b)
-        # x6 operands (fp32-accurate bf16x6) for the k3 s1 layers: three-plane packs of the same fragment orders
-        # (the input gradient's taps reversed by flipping the weight); launches that write t keep the fp32 packs
-        self.fwd6 = self.bwd6 = None
-        if (x6 and stride == 2 and self.KS in (1, 3) and not fwd_only and self.Cin in (128, 192)
-                and self.it_b in X6_IT):
-            # the k3 s2 input gradient (x6 conv_up, ica_conv_x6.hip pick_up3s2_x6) and the 1x1 s2 skips' (one tap in
-            # output class (0, 0)): conv_up fragment order
-            self.bwd6 = K.pack_conv_x6(w, self.Cin, self.Cout, self.KS, KK, self.Cin * KK, K.ORDER_UP, self.it_b)
-        if x6 and stride == 2 and self.KS == 3 and self.Cin >= 16 and mask is None and self.it in X6_IT:
-            # the k3 s2 forward (cheng2020 g_a.2 / g_a.4 conv1, leaky ReLU; ica_conv.hip pick_down_x6o_s2)
-            self.fwd6 = K.pack_conv_x6(w, self.Cout, self.Cin, 3, self.Cin * KK, KK, K.ORDER_DOWN, self.it)
-        if x6 and stride == 1 and self.KS == 3 and self.Cin >= 16 and mask is None and self.it in X6_IT:
-            self.fwd6 = K.pack_conv_x6(w, self.Cout, self.Cin, 3, self.Cin * KK, KK, K.ORDER_DOWN, self.it)
-            if not fwd_only and self.Cout >= 16 and self.it_b in X6_IT:
-                self.bwd6 = K.pack_conv_x6(w.flip(-1, -2).contiguous(), self.Cin, self.Cout, 3, KK, self.Cin * KK,
-                                           K.ORDER_DOWN, self.it_b)
-
-    def forward(self, x4, epi=K.EPI_BIAS, **kw):
-        if self.fwd6 is not None and _x6_ok(kw):
-            return K.conv_ex(x4, self.Cin, self.fwd6, self.bias, self.Cout, self.KS, self.S, 0, epi, self.it,
-                             prec=self.p6, **kw)
-        return K.conv_ex(x4, self.Cin, self.fwd, self.bias, self.Cout, self.KS, self.S, 0, epi, self.it, **kw)
-
-    def dgrad(self, g4, epi=K.EPI_BIAS, **kw):
-        if self.S == 1:
-            if self.bwd6 is not None and _x6_ok(kw):
-                return K.conv_ex(g4, self.Cout, self.bwd6, None, self.Cin, self.KS, 1, 0, epi, self.it_b,
-                                 prec=self.p6, **kw)
-            return K.conv_ex(g4, self.Cout, self.bwd, None, self.Cin, self.KS, 1, 0, epi, self.it_b, **kw)
-        if self.bwd6 is not None and epi == K.EPI_BIAS and _x6_ok(kw):
-            return K.conv_ex(g4, self.Cout, self.bwd6, None, self.Cin, self.KS, 2, 1, epi, self.it_b,
-                             prec=K.PREC_X6, **kw)
-        return K.conv_ex(g4, self.Cout, self.bwd, None, self.Cin, self.KS, 2, 1, epi, self.it_b, **kw)
-
-
 def _x6_ok(kw):
     """An x6 k3 s1 launch: any fill (plain, leaky-ReLU mask, PixelUnshuffle), no t output (ica_conv.hip
     pick_down_x6o)."""
     return kw.get("save_t") is None
 
 
+class Conv3:
+    """One Conv2d(k in {1,3,5}, stride s, pad k//2) layer, packed for its forward and its input gradient: the fp32
+    packs (fwd, bwd) and, where an x6 kernel reads them, the three-plane packs of the same fragment orders (fwd6,
+    bwd6; launches that write t keep the fp32 packs)."""
+
+    def __init__(self, w, b, stride=1, fwd_only=False, mask=None, x6=False, b1=False):
+        """b1 (with x6): the X6O conv_down launches (k3 s1 forward / input gradient, k3 s2 forward) run bf16
+        operands over fp32 activations (hip_ops.PREC_B1: the x6 pack's hi plane); the stride-2 input gradients keep
+        x6 (cheng2020 --precision bf16)."""
+        w = w.detach()
+        self.p6 = p6 = K.PREC_B1 if b1 else K.PREC_X6
+        if mask is not None:
+            w = (w * mask.to(w.device)).contiguous()
+        self.Cout, self.Cin, self.KS = Co, Ci, KS = w.shape[0], w.shape[1], w.shape[-1]
+        self.S = stride
+        KK = KS * KS
+        it, it_b = _it(Co), _it(Ci)
+        self.fwd = K.pack_conv(w, Co, Ci, KS, Ci * KK, KK, K.ORDER_DOWN, 4 if Ci <= 4 else 16, it=it)
+        self.bias = None if b is None else b.detach().contiguous()
+        self.bwd = self.fwd6 = self.bwd6 = None
+        if x6 and KS == 3 and stride in (1, 2) and Ci >= 16 and mask is None and it in X6_IT:
+            # the k3 s1 forward and the k3 s2 one (cheng2020 g_a.2 / g_a.4 conv1; ica_conv.hip pick_down_x6o_s2)
+            self.fwd6 = K.pack_conv_x6(w, Co, Ci, 3, Ci * KK, KK, K.ORDER_DOWN, it, p6)
+        if fwd_only:
+            return
+        if stride == 1:   # dgrad = conv with the taps reversed, channels swapped
+            self.bwd = K.pack_conv(w, Ci, Co, KS, KK, Ci * KK, K.ORDER_DOWN, 16, flip=True, it=it_b)
+            if self.fwd6 is not None and Co >= 16 and it_b in X6_IT:
+                self.bwd6 = K.pack_conv_x6(w, Ci, Co, 3, KK, Ci * KK, K.ORDER_DOWN, it_b, p6, flip=True)
+        else:             # dgrad = stride-2 transposed conv (conv_up, KS in {3, 1})
+            self.bwd = K.pack_conv(w, Ci, Co, KS, KK, Ci * KK, K.ORDER_UP, 16, it=it_b)
+            if x6 and stride == 2 and KS in (1, 3) and Ci in (128, 192) and it_b in X6_IT:
+                # x6 conv_up (ica_conv_x6.hip pick_up3s2_x6; the 1x1 skips: one tap in output class (0, 0)), bias
+                # epilogue only; x6 under b1 too
+                self.bwd6 = K.pack_conv_x6(w, Ci, Co, KS, KK, Ci * KK, K.ORDER_UP, it_b)
+
+    def forward(self, x4, epi=K.EPI_BIAS, **kw):
+        wp = self.fwd6 if self.fwd6 is not None and _x6_ok(kw) else self.fwd
+        return K.conv_ex(x4, self.Cin, wp, self.bias, self.Cout, self.KS, self.S, 0, epi, **kw)
+
+    def dgrad(self, g4, epi=K.EPI_BIAS, **kw):
+        x6 = self.bwd6 is not None and _x6_ok(kw) and (self.S == 1 or epi == K.EPI_BIAS)
+        return K.conv_ex(g4, self.Cout, self.bwd6 if x6 else self.bwd, None, self.Cin, self.KS, self.S,
+                         0 if self.S == 1 else 1, epi, **kw)
+
+
 class Subpel:
     """subpel_conv3x3(Cin, C, 2) = Conv2d(Cin, 4C, 3, p=1) + PixelShuffle(2), rho-ordered rows."""
 
     def __init__(self, w, b, fwd_only=False, x6=False, b1=False):
-        self.p6 = K.PREC_B1 if b1 else K.PREC_X6   # as Conv3
+        self.p6 = p6 = K.PREC_B1 if b1 else K.PREC_X6   # as Conv3
         self.C = w.shape[0] // 4
-        self.Cin = w.shape[1]
+        self.Cin = Ci = w.shape[1]
         wr, self.bias = _rho_weight(w, b, self.C)
-        self.R = wr.shape[0]          # rho rows = 16 * ceil(C / 4)
-        self.it = 6 if self.R == 768 else (4 if self.R % 128 == 0 else _it(self.R))   # N = 192 / 128 / g_s.7
-        self.fwd = K.pack_conv(wr, self.R, self.Cin, 3, self.Cin * 9, 9, K.ORDER_DOWN, 16, it=self.it)
+        self.R = R = wr.shape[0]          # rho rows = 16 * ceil(C / 4)
+        it = 6 if R == 768 else (4 if R % 128 == 0 else _it(R))   # N = 192 / 128 / g_s.7
+        it_b = _it(Ci)
+        self.fwd = K.pack_conv(wr, R, Ci, 3, Ci * 9, 9, K.ORDER_DOWN, 16, it=it)
         # x6 forward (PixelShuffle store) and input gradient (PixelUnshuffle fill, the flipped weight)
-        self.fwd6 = (K.pack_conv_x6(wr, self.R, self.Cin, 3, self.Cin * 9, 9, K.ORDER_DOWN, self.it)
-                     if x6 and self.Cin >= 16 and self.it in X6_IT_PS else None)
-        self.it_b = _it(self.Cin)
-        self.bwd = None if fwd_only else K.pack_conv(wr, self.Cin, self.R, 3, 9, self.Cin * 9, K.ORDER_DOWN, 16,
-                                                     flip=True, it=self.it_b)
-        self.bwd6 = (K.pack_conv_x6(wr.flip(-1, -2).contiguous(), self.Cin, self.R, 3, 9, self.Cin * 9,
-                                    K.ORDER_DOWN, self.it_b)
-                     if x6 and not fwd_only and self.R >= 16 and self.it_b in X6_IT else None)
+        self.fwd6 = (K.pack_conv_x6(wr, R, Ci, 3, Ci * 9, 9, K.ORDER_DOWN, it, p6)
+                     if x6 and Ci >= 16 and it in X6_IT_PS else None)
+        self.bwd = None if fwd_only else K.pack_conv(wr, Ci, R, 3, 9, Ci * 9, K.ORDER_DOWN, 16, flip=True, it=it_b)
+        self.bwd6 = (K.pack_conv_x6(wr, Ci, R, 3, 9, Ci * 9, K.ORDER_DOWN, it_b, p6, flip=True)
+                     if x6 and not fwd_only and R >= 16 and it_b in X6_IT else None)
 
     def forward(self, x4, epi=K.EPI_BIAS, **kw):
         # x6 at IT = 1 (g_s.7's 16 rho rows) is built for the bias epilogue only (ica_conv.hip pick_down_x6o)
-        if self.fwd6 is not None and _x6_ok(kw) and (self.it != 1 or epi == K.EPI_BIAS):
-            return K.conv_ex(x4, self.Cin, self.fwd6, self.bias, self.R, 3, 1, 0, epi, self.it, ps=True,
-                             alg_rows=4 * self.C, prec=self.p6, **kw)
-        return K.conv_ex(x4, self.Cin, self.fwd, self.bias, self.R, 3, 1, 0, epi, self.it, ps=True,
+        x6 = self.fwd6 is not None and _x6_ok(kw) and (self.fwd6.it != 1 or epi == K.EPI_BIAS)
+        return K.conv_ex(x4, self.Cin, self.fwd6 if x6 else self.fwd, self.bias, self.R, 3, 1, 0, epi, ps=True,
                          alg_rows=4 * self.C, **kw)
 
     def dgrad(self, g4, **kw):
         """g4: gradient of the shuffled output [N, C/4, 2H, 2W, 4] -> gradient of the input [N, Cin, H, W]."""
-        if self.bwd6 is not None and _x6_ok(kw):
-            return K.conv_ex(g4, self.R, self.bwd6, None, self.Cin, 3, 1, 0, K.EPI_BIAS, self.it_b,
-                             fill_mode=K.FILL_UNSHUFFLE, alg_rows=4 * self.C, prec=self.p6, **kw)
-        return K.conv_ex(g4, self.R, self.bwd, None, self.Cin, 3, 1, 0, K.EPI_BIAS, self.it_b,
-                         fill_mode=K.FILL_UNSHUFFLE, alg_rows=4 * self.C, **kw)
+        wp = self.bwd6 if self.bwd6 is not None and _x6_ok(kw) else self.bwd
+        return K.conv_ex(g4, self.R, wp, None, self.Cin, 3, 1, 0, K.EPI_BIAS, fill_mode=K.FILL_UNSHUFFLE,
+                         alg_rows=4 * self.C, **kw)
 
 
 def _gdn(sd, pre):

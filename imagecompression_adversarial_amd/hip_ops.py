@@ -14,8 +14,12 @@ from ._lib import ConvArgs, call, lib, ptr, stream
 
 EPI_BIAS, EPI_RELU, EPI_GDN, EPI_IGDN, EPI_GDN_BWD, EPI_IGDN_BWD, EPI_LRELU, EPI_LRELU_BWD = range(8)
 FILL_PLAIN, FILL_LRELU_MASK, FILL_UNSHUFFLE = range(3)
+# fragment orders of a packed weight (include/ica_hip.h ICA_ORDER_*): every layout a kernel reads has its own
 ORDER_DOWN, ORDER_UP = 0, 1
-ORDER_RGB5 = 2   # ica_pack_conv_weight_x6: dense tap-row pack of a k5 conv_down with <= 3 input channels
+ORDER_RGB5 = 2   # dense tap-row pack of a k5 conv_down with <= 3 input channels (bf16 and x6)
+ORDER_TG = 3     # bf16 4-tap groups of a conv_down with <= 4 input channels
+ORDER_UP3 = 4    # Z-gather pack of the conv_up to 3 channels (ica_conv_up3*)
+_ORDER_NAME = ("DOWN", "UP", "RGB5", "TG", "UP3")
 # parity-split tensors of an x6 k5 s2 launch (ica_conv_args.layout): the input x, the output-layout tensors
 LAYOUT_IN, LAYOUT_OUT = 1, 2
 GDN_BETA_BOUND = float((1e-6 + 2.0 ** -36) ** 0.5)  # NonNegativeParametrizer bound (utils/ops.py:67)
@@ -161,29 +165,6 @@ def from_nc4(x4: torch.Tensor, C: int) -> torch.Tensor:
 # --------------------------------------------------------------------------- #
 # Weight packing
 # --------------------------------------------------------------------------- #
-def pack_conv(w: torch.Tensor, O: int, Cc: int, KS: int, so: int, sc: int, order: int, CC: int,
-              flip: bool = False, it: int = 0) -> torch.Tensor:
-    """Pack a conv weight viewed as W[o][c][ky][kx] (strides so, sc; k contiguous); flip reverses the taps;
-    it = 32-channel row tiles per wave (0: the library default for O)."""
-    w = w.detach().contiguous()
-    _dev_check(w, "weight")
-    n = int(lib().ica_pack_conv_weight_size(O, Cc, KS, CC, it))
-    dst = torch.empty(n, dtype=torch.float32, device=w.device)
-    call("ica_pack_conv_weight", ptr(w), ptr(dst), O, Cc, KS, so, sc, CC, order, int(flip), it, stream())
-    return dst
-
-
-def pack_conv_bf16(w: torch.Tensor, O: int, Cc: int, KS: int, so: int, sc: int, order: int, flip: bool = False,
-                   it: int = 0) -> torch.Tensor:
-    """bf16 fragments (prec=1 launches): the CC=16 fp32 fragment order, each element rounded to bf16."""
-    w = w.detach().contiguous()
-    _dev_check(w, "weight")
-    n = int(lib().ica_pack_conv_weight_bf16_size(O, Cc, KS, it))
-    dst = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-    call("ica_pack_conv_weight_bf16", ptr(w), ptr(dst), O, Cc, KS, so, sc, order, int(flip), it, stream())
-    return dst
-
-
 PREC_FP32, PREC_BF16, PREC_X6 = 0, 1, 2
 # bf16 operands over fp32 activations: the k3 conv_downs (cheng2020 --precision bf16) on the hi plane of the x6 pack
 # (RNE bf16 of activations and weights, fp32 accumulate, fp32 tensors; GDN epilogue GEMMs on the x6 gamma' pack)
@@ -191,27 +172,75 @@ PREC_B1 = 3
 
 
 def x6_it(O: int) -> int:
-    """Row tiles per wave of an x6 launch (the library default for O: 4 for 128 channels, 3 for 192)."""
+    """Row tiles per wave the library uses by default for O output channels (4 for 128 channels, 3 for 192)."""
     return int(lib().ica_conv_it(O))
 
 
-def pack_conv_x6(w: torch.Tensor, O: int, Cc: int, KS: int, so: int, sc: int, order: int, it: int) -> torch.Tensor:
-    """fp32-accurate bf16x6 fragments (prec=2 launches, ica_conv_x6.hip): three bf16 planes (hi, mid, lo: an exact
-    split of each weight) of the CC=16 fragment order."""
+class Pack:
+    """Packed weight fragments and what they are: W[O][C][KS][KS] in fragment order `order` (ORDER_*), operands
+    `prec` (PREC_*), `it` row tiles per wave (resolved, > 0), taps reversed if `flip`.  kind: the launch that reads
+    it (0 conv_down, 1 conv_up; ORDER_UP3 is the conv_up to 3 channels).  The launch wrappers take prec and it from
+    here and refuse a launch whose geometry or kind differs."""
+    __slots__ = ("data", "O", "C", "KS", "kind", "order", "prec", "it", "flip")
+
+    def __init__(self, data, O, C, KS, order, prec=PREC_FP32, it=0, flip=False):
+        self.data, self.O, self.C, self.KS = data, int(O), int(C), int(KS)
+        self.order, self.prec, self.flip = int(order), int(prec), bool(flip)
+        self.kind = 1 if order in (ORDER_UP, ORDER_UP3) else 0
+        self.it = int(it) if it > 0 else x6_it(O)
+
+    def __repr__(self):
+        return (f"Pack(O={self.O}, C={self.C}, KS={self.KS}, kind={self.kind}, order={_ORDER_NAME[self.order]}, "
+                f"prec={_PREC_SUFFIX[self.prec]}, it={self.it}, flip={self.flip})")
+
+
+def _weight(w):
     w = w.detach().contiguous()
     _dev_check(w, "weight")
+    return w
+
+
+def pack_conv(w: torch.Tensor, O: int, Cc: int, KS: int, so: int, sc: int, order: int, CC: int,
+              flip: bool = False, it: int = 0) -> Pack:
+    """Pack a conv weight viewed as W[o][c][ky][kx] (strides so, sc; k contiguous); flip reverses the taps;
+    it = 32-channel row tiles per wave (0: the library default for O)."""
+    w = _weight(w)
+    n = int(lib().ica_pack_conv_weight_size(O, Cc, KS, CC, it))
+    dst = torch.empty(n, dtype=torch.float32, device=w.device)
+    call("ica_pack_conv_weight", ptr(w), ptr(dst), O, Cc, KS, so, sc, CC, order, int(flip), it, stream())
+    return Pack(dst, O, Cc, KS, order, PREC_FP32, it, flip)
+
+
+def pack_conv_bf16(w: torch.Tensor, O: int, Cc: int, KS: int, so: int, sc: int, order: int, flip: bool = False,
+                   it: int = 0) -> Pack:
+    """bf16 fragments (PREC_BF16 launches): the CC=16 fp32 fragment order, each element rounded to bf16.  Cc <= 4
+    with ORDER_DOWN writes the 4-tap groups of an RGB conv input: that pack is ORDER_TG."""
+    w = _weight(w)
+    n = int(lib().ica_pack_conv_weight_bf16_size(O, Cc, KS, it))
+    dst = torch.empty(n, dtype=torch.bfloat16, device=w.device)
+    call("ica_pack_conv_weight_bf16", ptr(w), ptr(dst), O, Cc, KS, so, sc, order, int(flip), it, stream())
+    return Pack(dst, O, Cc, KS, ORDER_TG if (Cc <= 4 and order == ORDER_DOWN) else order, PREC_BF16, it, flip)
+
+
+def pack_conv_x6(w: torch.Tensor, O: int, Cc: int, KS: int, so: int, sc: int, order: int, it: int,
+                 prec: int = PREC_X6, flip: bool = False) -> Pack:
+    """fp32-accurate bf16x6 fragments (PREC_X6 launches, ica_conv_x6.hip): three bf16 planes (hi, mid, lo: an exact
+    split of each weight) of the CC=16 fragment order.  prec=PREC_B1: the same bytes, launched on the hi plane
+    only.  flip packs the weight with its taps reversed."""
+    w = _weight(w.flip(-1, -2) if flip else w)
     n = int(lib().ica_pack_conv_weight_x6_size(O, Cc, KS, it))
     dst = torch.empty(n, dtype=torch.bfloat16, device=w.device)
     call("ica_pack_conv_weight_x6", ptr(w), ptr(dst), O, Cc, KS, so, sc, order, it, stream())
-    return dst
+    return Pack(dst, O, Cc, KS, order, prec, it, flip)
 
 
 def x6_ok(O: int, C: int, it: int, kind: int) -> bool:
-    """Shapes ica_conv_x6_dispatch (ica_conv_x6.hip) covers for a k5 s2 launch with O output / C input channels:
-    kind 0 (conv_down): C >= 16, a multiple of 16; O = 128-multiples (IT 4: bias, GDN, IGDN_BWD) or 96-multiples
-    (IT 3: bias only -- the only IT 3 conv_downs, g_a.6 forward and the g_s.0 input gradient, have no epilogue);
-    kind 1 (conv_up): IT 4 only (O a 128-multiple) with C = 64, 128 or a 64-multiple.  No explicit-IT (C = 192 GDN)
-    launch.  Anything else keeps the fp32 pack."""
+    """Whether PackedConv packs a k5 s2 launch with O output / C input channels for ica_conv_x6_dispatch
+    (ica_conv_x6.hip): kind 0 (conv_down): C >= 16, a multiple of 16; O = 128-multiples (IT 4: bias, GDN, IGDN_BWD)
+    or 96-multiples (IT 3: bias only -- the only IT 3 conv_downs, g_a.6 forward and the g_s.0 input gradient, have
+    no epilogue); kind 1 (conv_up): IT 4 only (O a 128-multiple) with C = 64, 128 or a 64-multiple.  No explicit-IT
+    (C = 192 GDN) launch.  Anything else keeps the fp32 pack.  This only chooses the pack: the launch carries the
+    pack's order and precision, and the library rejects (-4) a pack its route does not read."""
     if it != 0 or C < 16 or C % 16:
         return False
     if kind == 0:
@@ -223,10 +252,9 @@ def conv_cc(Cin: int) -> int:
     return 4 if Cin <= 4 else 16
 
 
-def pack_up3(w_view: torch.Tensor, prec: int = 0) -> torch.Tensor:
+def pack_up3(w_view: torch.Tensor, prec: int = 0) -> Pack:
     """Fragments for conv_up3 from a [Cin][3][5][5] transposed-conv weight view (prec 1: bf16, 2: x6)."""
-    w = w_view.detach().contiguous()
-    _dev_check(w, "weight")
+    w = _weight(w_view)
     Cin = w.shape[0]
     n = int(lib().ica_pack_up3_size(Cin))
     if prec == PREC_X6:
@@ -238,7 +266,35 @@ def pack_up3(w_view: torch.Tensor, prec: int = 0) -> torch.Tensor:
     else:
         dst = torch.empty(n, device=w.device)
         call("ica_pack_up3", ptr(w), ptr(dst), Cin, stream())
-    return dst
+    return Pack(dst, 3, Cin, 5, ORDER_UP3, prec)
+
+
+def _pack_down(w, O, C, KS, S, so, sc, it, prec) -> Pack:
+    """The pack of a conv_down launch (a conv's forward, a deconv's input gradient).  k5 s2 under PREC_BF16: bf16
+    fragments (16-channel chunks, 4-tap groups for <= 4 input channels); under PREC_X6: x6 fragments where x6_ok.
+    An RGB-sized input into 128 channels gets the dense tap-row pack (conv_rgb5_bf16 / conv_rgb5_x6: the 75 (tap,
+    channel) pairs in 5 K steps).  Everything else, explicit 6-tile x6 layers included, is fp32."""
+    if KS == 5 and S == 2:
+        rgb5 = C <= 3 and O == 128
+        if prec == PREC_BF16 and (C >= 16 or C <= 4):
+            return pack_conv_bf16(w, O, C, 5, so, sc, ORDER_RGB5 if rgb5 and it in (0, 4) else ORDER_DOWN, it=it)
+        if prec == PREC_X6 and rgb5 and it == 0:
+            return pack_conv_x6(w, O, C, 5, so, sc, ORDER_RGB5, 4)
+        if prec == PREC_X6 and x6_ok(O, C, it, 0):
+            return pack_conv_x6(w, O, C, 5, so, sc, ORDER_DOWN, x6_it(O))
+    return pack_conv(w, O, C, KS, so, sc, ORDER_DOWN, conv_cc(C), it=it)
+
+
+def _pack_up(w, O, C, KS, S, so, sc, it, prec) -> Pack:
+    """The pack of a conv_up launch (a deconv's forward, a k5 s2 conv's input gradient; w viewed [C][O][k][k]):
+    the Z-gather pack for 3 output channels, else as _pack_down."""
+    if O == 3 and KS == 5:
+        return pack_up3(w, prec)
+    if KS == 5 and prec == PREC_BF16:
+        return pack_conv_bf16(w, O, C, 5, so, sc, ORDER_UP, it=it)
+    if KS == 5 and S == 2 and prec == PREC_X6 and x6_ok(O, C, it, 1):
+        return pack_conv_x6(w, O, C, 5, so, sc, ORDER_UP, x6_it(O))
+    return pack_conv(w, O, C, KS, so, sc, ORDER_UP, 16, it=it)
 
 
 class PackedConv:
@@ -250,110 +306,35 @@ class PackedConv:
 
     def __init__(self, weight: torch.Tensor, bias, kind: str, stride: int, prec: int = PREC_FP32,
                  it_fwd: int = 0, it_bwd: int = 0):
-        """prec=PREC_BF16 packs the k5 s2 layers as bf16 fragments (fwd_prec / bwd_prec record what each pack
-        is): 16-channel chunks, 4-tap groups for an RGB conv input, the Z-gather pack for 3-channel outputs.
+        """prec=PREC_BF16 / PREC_X6 packs the k5 s2 layers as bf16 / x6 fragments where a kernel reads them
+        (_pack_down / _pack_up); fwd_prec / bwd_prec are what each pack is.
         it_fwd / it_bwd: 32-channel row tiles per wave of the forward / input-gradient launches (0 = the library
         default; 6 for the C = 192 GDN layers of bmshj2018 q6-8, whose epilogue needs all channels in one wave; the
         bf16 path has IT = 6 kernels for those GDN / IGDN layers and their input gradients too)."""
-        self.it_fwd, self.it_bwd = it_fwd, it_bwd
-        if prec == PREC_X6:
-            self._init_x6(weight, bias, kind, stride)
-            return
-        self.kind = kind
-        self.fwd_prec = self.bwd_prec = PREC_FP32
-        self.stride = stride
-        self.KS = weight.shape[-1]
-        KK = self.KS * self.KS
+        self.kind, self.stride = kind, stride
+        self.KS = KS = weight.shape[-1]
+        KK = KS * KS
         if kind == "conv":
-            self.Cout, self.Cin = weight.shape[0], weight.shape[1]
-            # forward: o = co, c = ci
-            if prec == PREC_BF16 and self.KS == 5 and stride == 2 and (self.Cin >= 16 or self.Cin <= 4):
-                # an RGB input into 128 channels: the dense tap-row pack of conv_rgb5_bf16 (ica_conv_ex routes those
-                # launches there); other shapes keep the tap groups / 16-channel chunks
-                rgb5 = self.Cin <= 3 and self.Cout == 128 and it_fwd in (0, 4)
-                self.fwd = pack_conv_bf16(weight, self.Cout, self.Cin, 5, self.Cin * KK, KK,
-                                          ORDER_RGB5 if rgb5 else ORDER_DOWN, it=it_fwd)
-                self.fwd_prec = PREC_BF16
-            else:
-                self.fwd = pack_conv(weight, self.Cout, self.Cin, self.KS, self.Cin * KK, KK, ORDER_DOWN,
-                                     conv_cc(self.Cin), it=it_fwd)
+            self.Cout, self.Cin = Co, Ci = weight.shape[0], weight.shape[1]
+            self.fwd = _pack_down(weight, Co, Ci, KS, stride, Ci * KK, KK, it_fwd, prec)   # o = co, c = ci
             # dgrad: k5 s2 -> conv_up (o = ci, c = co); k3 s1 -> conv_down with the taps reversed
             self.bwd = None
-            if self.KS == 3 and stride == 1 and self.Cout % 16 == 0:
-                self.bwd = pack_conv(weight, self.Cin, self.Cout, 3, KK, self.Cin * KK, ORDER_DOWN,
-                                     conv_cc(self.Cout), flip=True)
-            elif self.KS == 5 and stride == 2 and self.Cout % 16 == 0:
-                if self.Cin == 3:   # input-gradient of the first conv: Z-gather kernel
-                    self.bwd = pack_up3(weight, prec)
-                    self.bwd_prec = prec
-                elif prec == PREC_BF16:
-                    self.bwd = pack_conv_bf16(weight, self.Cin, self.Cout, 5, KK, self.Cin * KK, ORDER_UP, it=it_bwd)
-                    self.bwd_prec = PREC_BF16
-                else:
-                    self.bwd = pack_conv(weight, self.Cin, self.Cout, self.KS, KK, self.Cin * KK, ORDER_UP, 16,
-                                         it=it_bwd)
+            if KS == 3 and stride == 1 and Co % 16 == 0:
+                self.bwd = pack_conv(weight, Ci, Co, 3, KK, Ci * KK, ORDER_DOWN, conv_cc(Co), flip=True)
+            elif KS == 5 and stride == 2 and Co % 16 == 0:
+                self.bwd = _pack_up(weight, Ci, Co, 5, 2, KK, Ci * KK, it_bwd, prec)
         elif kind == "deconv":
-            self.Cin, self.Cout = weight.shape[0], weight.shape[1]
-            # forward (conv_up): o = co, c = ci
-            if self.Cout == 3 and self.KS == 5:
-                self.fwd = pack_up3(weight, prec)
-                self.fwd_prec = prec
-            elif prec == PREC_BF16 and self.KS == 5:
-                self.fwd = pack_conv_bf16(weight, self.Cout, self.Cin, 5, KK, self.Cout * KK, ORDER_UP, it=it_fwd)
-                self.fwd_prec = PREC_BF16
-            else:
-                self.fwd = pack_conv(weight, self.Cout, self.Cin, self.KS, KK, self.Cout * KK, ORDER_UP, 16,
-                                     it=it_fwd)
-            # dgrad (conv_down, stride 2): o = ci, c = co
-            if prec == PREC_BF16 and self.KS == 5 and stride == 2 and (self.Cout >= 16 or self.Cout <= 4):
-                rgb5 = self.Cout <= 3 and self.Cin == 128 and it_bwd in (0, 4)
-                self.bwd = pack_conv_bf16(weight, self.Cin, self.Cout, 5, self.Cout * KK, KK,
-                                          ORDER_RGB5 if rgb5 else ORDER_DOWN, it=it_bwd)
-                self.bwd_prec = PREC_BF16
-            else:
-                self.bwd = pack_conv(weight, self.Cin, self.Cout, self.KS, self.Cout * KK, KK, ORDER_DOWN,
-                                     conv_cc(self.Cout), it=it_bwd)
+            self.Cin, self.Cout = Ci, Co = weight.shape[0], weight.shape[1]
+            self.fwd = _pack_up(weight, Co, Ci, KS, stride, KK, Co * KK, it_fwd, prec)     # o = co, c = ci
+            self.bwd = _pack_down(weight, Ci, Co, KS, stride, Co * KK, KK, it_bwd, prec)   # o = ci, c = co
         else:
             raise ValueError(kind)
         self.bias = None if bias is None else bias.detach().contiguous()
 
-    def _init_x6(self, weight, bias, kind, stride):
-        """PREC_X6: the k5 s2 launches run on the bf16x6 kernels: >= 16 channels on both ends (conv_down_x6 /
-        conv_up_x6) and the conv_downs whose input has <= 3 channels (g_a.0 forward, g_s.6 input gradient: conv_rgb5_x6
-        with the 75 (tap, channel) pairs packed densely into 5 K steps) and the 3-channel transposed-conv outputs (x6 conv_up3).  Explicit 6-tile layers
-        keep the fp32 packs."""
-        fp = PackedConv(weight, bias, kind, stride, PREC_FP32, self.it_fwd, self.it_bwd)
-        self.__dict__.update(fp.__dict__)
-        if self.KS != 5 or stride != 2:
-            return
-        KK = 25
-        rgb_ok = lambda O, C, it: it == 0 and C <= 3 and O == 128   # noqa: E731  (conv_rgb5_x6: one 128-row block)
-        if kind == "conv" and self.Cin == 3 and self.Cout % 16 == 0:    # input gradient to RGB: x6 conv_up3
-            self.bwd = pack_up3(weight, PREC_X6)
-            self.bwd_prec = PREC_X6
-        if kind == "deconv" and self.Cout == 3 and self.Cin % 16 == 0:  # g_s.6 forward to RGB: x6 conv_up3
-            self.fwd = pack_up3(weight, PREC_X6)
-            self.fwd_prec = PREC_X6
-        if kind == "conv":
-            if rgb_ok(self.Cout, self.Cin, self.it_fwd):   # forward from the RGB image: dense tap-row K
-                self.fwd = pack_conv_x6(weight, self.Cout, self.Cin, 5, self.Cin * KK, KK, ORDER_RGB5, 4)
-                self.fwd_prec = PREC_X6
-            elif x6_ok(self.Cout, self.Cin, self.it_fwd, 0):  # forward conv_down: o = co, c = ci
-                self.fwd = pack_conv_x6(weight, self.Cout, self.Cin, 5, self.Cin * KK, KK, ORDER_DOWN, x6_it(self.Cout))
-                self.fwd_prec = PREC_X6
-            if self.Cin != 3 and x6_ok(self.Cin, self.Cout, self.it_bwd, 1):   # dgrad conv_up: o = ci, c = co
-                self.bwd = pack_conv_x6(weight, self.Cin, self.Cout, 5, KK, self.Cin * KK, ORDER_UP, x6_it(self.Cin))
-                self.bwd_prec = PREC_X6
-        else:
-            if self.Cout != 3 and x6_ok(self.Cout, self.Cin, self.it_fwd, 1):  # forward conv_up: o = co, c = ci
-                self.fwd = pack_conv_x6(weight, self.Cout, self.Cin, 5, KK, self.Cout * KK, ORDER_UP, x6_it(self.Cout))
-                self.fwd_prec = PREC_X6
-            if rgb_ok(self.Cin, self.Cout, self.it_bwd):   # dgrad from the RGB-sized gradient (view [ci][co])
-                self.bwd = pack_conv_x6(weight, self.Cin, self.Cout, 5, self.Cout * KK, KK, ORDER_RGB5, 4)
-                self.bwd_prec = PREC_X6
-            elif x6_ok(self.Cin, self.Cout, self.it_bwd, 0):    # dgrad conv_down: o = ci, c = co
-                self.bwd = pack_conv_x6(weight, self.Cin, self.Cout, 5, self.Cout * KK, KK, ORDER_DOWN, x6_it(self.Cin))
-                self.bwd_prec = PREC_X6
+    fwd_prec = property(lambda self: self.fwd.prec)
+    bwd_prec = property(lambda self: PREC_FP32 if self.bwd is None else self.bwd.prec)
+    it_fwd = property(lambda self: self.fwd.it)
+    it_bwd = property(lambda self: 0 if self.bwd is None else self.bwd.it)
 
 
 class PackedGDN:
@@ -400,101 +381,93 @@ class PackedGDN:
 # --------------------------------------------------------------------------- #
 # Convolutions
 # --------------------------------------------------------------------------- #
-def conv_down(x4, Cin, wp, bias, Cout, KS, S, epi=EPI_BIAS, gdn: PackedGDN | None = None, save=False,
-              saved=None, out=None, tag=None, save_t=None, prec=PREC_FP32, it=0, layout=0):
-    """y = conv2d(x, W, stride S, pad KS//2) (+epilogue).  Returns (y4, save_x, save_s).
-    save_t: optional nChw4c output of t = dL/dn for the GDN-bwd epilogues (GDN parameter gradients).
-    prec=PREC_BF16: bf16-operand launch (wp from pack_conv_bf16; goes through ica_conv_ex).
-    it: the row-tile count wp was packed with (0 = library default; explicit values go through ica_conv_ex).
-    layout: parity-split tensors (LAYOUT_IN: x, LAYOUT_OUT: y and the saved / output-layout tensors; x6 only)."""
-    N, _, H, W, _ = x4.shape
-    tag = _prec_note(tag, prec)
-    if prec in (PREC_BF16, PREC_X6) or it or layout:
-        return _conv_prec(x4, Cin, wp, bias, Cout, KS, S, 0, epi, gdn, save, saved, out, tag, save_t, prec, it,
-                          layout)
-    Ho = (H + 2 * (KS // 2) - KS) // S + 1
-    Wo = (W + 2 * (KS // 2) - KS) // S + 1
-    y = out if out is not None else empty_nc4(N, Cout, Ho, Wo, x4.device)
+def _out_hw(H, W, KS, S, kind):
+    if kind == 0:
+        return (H + 2 * (KS // 2) - KS) // S + 1, (W + 2 * (KS // 2) - KS) // S + 1
+    return 2 * H, 2 * W
+
+
+def _check_pack(wp, Cin, Cout, KS, kind, prec=None, it=0):
+    """A launch runs only on a pack that says it is that launch's weight.  prec / it: what a caller still states
+    about the pack (nothing has to); a statement the pack contradicts is refused like any other mismatch."""
+    if not isinstance(wp, Pack):
+        raise TypeError(f"conv launch: wp must be a hip_ops.Pack (from a packer or a PackedConv), not "
+                        f"{type(wp).__name__}")
+    if (wp.O, wp.C, wp.KS, wp.kind) != (Cout, Cin, KS, kind):
+        raise ValueError(f"conv launch (O={Cout}, C={Cin}, KS={KS}, kind={kind}) on {wp!r}")
+    if (wp.data.dtype == torch.float32) != (wp.prec == PREC_FP32):
+        raise ValueError(f"{wp!r} holds {wp.data.dtype} fragments")
+    if (prec is not None and prec != wp.prec) or (it and it != wp.it):
+        raise ValueError(f"conv launch stated prec={prec}, it={it} for {wp!r}")
+
+
+def _conv3(x4, Cin, wp, bias, Cout, KS, S, kind, epi, gdn, save, saved, out, tag, save_t, layout, prec, it):
+    """conv_down / conv_up through conv_ex: allocates save_s, returns (y4, save_x, save_s)."""
+    _check_pack(wp, Cin, Cout, KS, kind, prec, it)
     ss = None
     if save and epi in (EPI_GDN, EPI_IGDN):
         # backward needs (y, s): y = x*s is this layer's output (kept alive anyway as the next
         # layer's input), so only s is written; the bwd epilogue recovers x = y / s.
-        ss = empty_nc4(N, Cout, Ho, Wo, x4.device)
-    in_x = in_s = None
-    if epi in (EPI_GDN_BWD, EPI_IGDN_BWD):
-        in_x, in_s = saved
-    ev = _ev_begin(tag, N)
-    call("ica_conv_down", ptr(x4), ptr(y), ptr(wp), ptr(bias), N, Cin, H, W, Cout, Ho, Wo, KS, S, epi,
-         ptr(None if gdn is None else (gdn.gpT if epi >= EPI_GDN_BWD else gdn.gp)),
-         ptr(None if gdn is None else gdn.beta), None, ptr(ss), ptr(in_x), ptr(in_s), ptr(save_t), stream())
-    _ev_end(ev)
+        N, _, H, W, _ = x4.shape
+        ss = empty_nc4(N, Cout, *_out_hw(H, W, KS, S, kind), x4.device,
+                       torch.bfloat16 if wp.prec == PREC_BF16 else torch.float32)
+    y = conv_ex(x4, Cin, wp, bias, Cout, KS, S, kind, epi, gdn, save_s=ss, saved=saved, save_t=save_t, out=out,
+                tag=tag, layout=layout, _flops=False)
     return y, (y if ss is not None else None), ss
 
 
-def conv_up(x4, Cin, wp, bias, Cout, epi=EPI_BIAS, gdn: PackedGDN | None = None, save=False, saved=None,
-            out=None, tag=None, save_t=None, prec=PREC_FP32, it=0, layout=0):
+def conv_down(x4, Cin, wp: Pack, bias, Cout, KS, S, epi=EPI_BIAS, gdn: PackedGDN | None = None, save=False,
+              saved=None, out=None, tag=None, save_t=None, layout=0, prec=None, it=0):
+    """y = conv2d(x, W, stride S, pad KS//2) (+epilogue).  Returns (y4, save_x, save_s).  Operand precision and
+    row tiles are the pack's (prec / it, if a caller states them, are only checked against it).
+    save_t: optional nChw4c output of t = dL/dn for the GDN-bwd epilogues (GDN parameter gradients).
+    layout: parity-split tensors (LAYOUT_IN: x, LAYOUT_OUT: y and the saved / output-layout tensors; x6 only)."""
+    return _conv3(x4, Cin, wp, bias, Cout, KS, S, 0, epi, gdn, save, saved, out, tag, save_t, layout, prec, it)
+
+
+def conv_up(x4, Cin, wp: Pack, bias, Cout, epi=EPI_BIAS, gdn: PackedGDN | None = None, save=False, saved=None,
+            out=None, tag=None, save_t=None, layout=0, prec=None, it=0):
     """y = conv_transpose2d(x, W, stride 2, pad 2, output_padding 1) (+epilogue).  layout: as conv_down (the
     3-channel output of conv_up3 is always row-major)."""
+    if Cout != 3:
+        return _conv3(x4, Cin, wp, bias, Cout, 5, 2, 1, epi, gdn, save, saved, out, tag, save_t, layout, prec, it)
+    _check_pack(wp, Cin, 3, 5, 1, prec, it)
+    if wp.order != ORDER_UP3:
+        raise ValueError(f"conv_up to 3 channels reads the Z-gather pack (ORDER_UP3), not {wp!r}")
+    if epi != EPI_BIAS:
+        raise RuntimeError("conv_up to 3 channels supports the bias epilogue only")
     N, _, H, W, _ = x4.shape
-    tag = _prec_note(tag, prec)
-    if (prec in (PREC_BF16, PREC_X6) or it or layout) and Cout != 3:
-        return _conv_prec(x4, Cin, wp, bias, Cout, 5, 2, 1, epi, gdn, save, saved, out, tag, save_t, prec, it,
-                          layout)
-    Ho, Wo = 2 * H, 2 * W
-    y = out if out is not None else empty_nc4(N, Cout, Ho, Wo, x4.device)
-    if Cout == 3:
-        if epi != EPI_BIAS:
-            raise RuntimeError("conv_up to 3 channels supports the bias epilogue only")
-        ev = _ev_begin(tag, N)
-        call({PREC_BF16: "ica_conv_up3_bf16", PREC_X6: "ica_conv_up3_x6"}.get(prec, "ica_conv_up3"), ptr(x4), ptr(y),
-             ptr(wp), ptr(bias), N, Cin, H, W, int(layout), stream())
-        _ev_end(ev)
-        return y, None, None
-    ss = None
-    if save and epi in (EPI_GDN, EPI_IGDN):
-        # backward needs (y, s): y = x*s is this layer's output (kept alive anyway as the next
-        # layer's input), so only s is written; the bwd epilogue recovers x = y / s.
-        ss = empty_nc4(N, Cout, Ho, Wo, x4.device)
-    in_x = in_s = None
-    if epi in (EPI_GDN_BWD, EPI_IGDN_BWD):
-        in_x, in_s = saved
-    ev = _ev_begin(tag, N)
-    call("ica_conv_up", ptr(x4), ptr(y), ptr(wp), ptr(bias), N, Cin, H, W, Cout, Ho, Wo, epi,
-         ptr(None if gdn is None else (gdn.gpT if epi >= EPI_GDN_BWD else gdn.gp)),
-         ptr(None if gdn is None else gdn.beta), None, ptr(ss), ptr(in_x), ptr(in_s), ptr(save_t), stream())
+    y = out if out is not None else empty_nc4(N, 3, 2 * H, 2 * W, x4.device)
+    ev = _ev_begin(_prec_note(tag, wp.prec), N)
+    call({PREC_BF16: "ica_conv_up3_bf16", PREC_X6: "ica_conv_up3_x6"}.get(wp.prec, "ica_conv_up3"), ptr(x4), ptr(y),
+         ptr(wp.data), ptr(bias), N, Cin, H, W, int(layout), stream())
     _ev_end(ev)
-    return y, (y if ss is not None else None), ss
+    return y, None, None
 
 
-def _conv_prec(x4, Cin, wp, bias, Cout, KS, S, kind, epi, gdn, save, saved, out, tag, save_t, prec, it, layout=0):
-    """conv_down / conv_up semantics (returns (y4, save_x, save_s)) through ica_conv_ex: bf16-operand launches and
-    explicit row-tile counts."""
-    N, _, H, W, _ = x4.shape
-    Ho, Wo = ((H + 2 * (KS // 2) - KS) // S + 1, (W + 2 * (KS // 2) - KS) // S + 1) if kind == 0 else (2 * H, 2 * W)
-    dt = torch.bfloat16 if prec == PREC_BF16 else torch.float32
-    ss = empty_nc4(N, Cout, Ho, Wo, x4.device, dt) if (save and epi in (EPI_GDN, EPI_IGDN)) else None
-    y = conv_ex(x4, Cin, wp, bias, Cout, KS, S, kind, epi, it, gdn, save_s=ss, saved=saved, save_t=save_t, out=out,
-                tag=tag, prec=prec, layout=layout)
-    return y, (y if ss is not None else None), ss
-
-
-def conv_ex(x4, Cin, wp, bias, Cout, KS, S, kind=0, epi=EPI_BIAS, it=0, gdn: PackedGDN | None = None, res=None,
+def conv_ex(x4, Cin, wp: Pack, bias, Cout, KS, S, kind=0, epi=EPI_BIAS, gdn: PackedGDN | None = None, res=None,
             save_x=None, save_s=None, saved=None, save_t=None, mask=None, fill_mode=FILL_PLAIN, ps=False,
-            out=None, tag=None, alg_rows=None, prec=PREC_FP32, layout=0):
-    """Generic conv launch (ica_conv_ex).  kind 0: conv2d(x, W, stride S, pad KS//2); kind 1: the stride-2
-    transposed conv (dgrad of a stride-2 conv).  fill_mode 2 views x ([N, Cin/16, 2H, 2W, 4]) as the
-    PixelUnshuffle(2) tensor [N, Cin/4, H, W, 4] in rho order; ps stores PixelShuffle(2) of the rho-ordered
-    Cout rows (y: [N, Cout/16, 2Ho, 2Wo, 4]).  save_x / save_s / save_t: caller-allocated outputs."""
+            out=None, tag=None, alg_rows=None, layout=0, prec=None, it=0, _flops=True):
+    """The conv launch (ica_conv_ex).  kind 0: conv2d(x, W, stride S, pad KS//2); kind 1: the stride-2
+    transposed conv (dgrad of a stride-2 conv).  Operand precision, row tiles and fragment order are the pack's;
+    a pack of another geometry or kind is refused (ValueError) before anything is launched.  fill_mode 2 views x
+    ([N, Cin/16, 2H, 2W, 4]) as the PixelUnshuffle(2) tensor [N, Cin/4, H, W, 4] in rho order; ps stores
+    PixelShuffle(2) of the rho-ordered Cout rows (y: [N, Cout/16, 2Ho, 2Wo, 4]).  save_x / save_s / save_t:
+    caller-allocated outputs."""
+    _check_pack(wp, Cin, Cout, KS, kind, prec, it)
+    if wp.order == ORDER_UP3:
+        raise ValueError(f"{wp!r} is launched by conv_up to 3 channels only")
+    if wp.order == ORDER_RGB5 and (epi not in (EPI_BIAS, EPI_GDN, EPI_IGDN_BWD) or fill_mode != FILL_PLAIN or ps
+                                   or any(t is not None for t in (res, save_x, save_t, mask))):
+        raise ValueError(f"{wp!r}: the dense tap-row pack is read by conv_rgb5 only (bias / GDN / IGDN_BWD epilogue, "
+                         f"plain fill, no extra tensors)")
+    prec = wp.prec
     N, C4x, H, W, _ = x4.shape
     if fill_mode == FILL_UNSHUFFLE:
         if Cin != 16 * C4x:
             raise RuntimeError("unshuffled conv input: Cin must be 16 * input channel groups")
         H, W = H // 2, W // 2
-    if kind == 0:
-        Ho = (H + 2 * (KS // 2) - KS) // S + 1
-        Wo = (W + 2 * (KS // 2) - KS) // S + 1
-    else:
-        Ho, Wo = 2 * H, 2 * W
+    Ho, Wo = _out_hw(H, W, KS, S, kind)
     dt = torch.bfloat16 if prec == PREC_BF16 else torch.float32   # bf16 path: bf16 activations
     if out is not None:
         y = out
@@ -515,21 +488,23 @@ def conv_ex(x4, Cin, wp, bias, Cout, KS, S, kind=0, epi=EPI_BIAS, it=0, gdn: Pac
             gp = gdn.gpxT if epi in (EPI_GDN_BWD, EPI_IGDN_BWD) else gdn.gpx
         else:   # fp32 epilogues (fp32 operands)
             gp = gdn.gpT if epi in (EPI_GDN_BWD, EPI_IGDN_BWD) else gdn.gp
-    a = ConvArgs(ptr(x4), ptr(y), ptr(wp), ptr(bias), ptr(gp), ptr(None if gdn is None else gdn.beta), ptr(save_x),
-                 ptr(save_s), ptr(in_x), ptr(in_s), ptr(save_t), ptr(res), ptr(mask), N, Cin, H, W, Cout, Ho, Wo,
-                 kind, KS, S, epi, it, fill_mode, int(bool(ps)), int(prec), int(layout))
+    a = ConvArgs(ptr(x4), ptr(y), ptr(wp.data), ptr(bias), ptr(gp), ptr(None if gdn is None else gdn.beta),
+                 ptr(save_x), ptr(save_s), ptr(in_x), ptr(in_s), ptr(save_t), ptr(res), ptr(mask), N, Cin, H, W, Cout,
+                 Ho, Wo, kind, KS, S, epi, wp.it, fill_mode, int(bool(ps)), prec, int(layout), wp.order)
     import ctypes
     tag = _prec_note(tag, prec)
     ev = _ev_begin(tag, N)
     call("ica_conv_ex", ctypes.c_void_p(ctypes.addressof(a)), stream())
     if ev is not None:
-        px = N * (H * W if kind == 1 else Ho * Wo)
-        # alg_rows: real (non-padding) rows of a rho-ordered subpel weight (4 * C)
-        cin_alg = alg_rows if (fill_mode == FILL_UNSHUFFLE and alg_rows) else Cin
-        cout_alg = alg_rows if (ps and alg_rows) else Cout
-        fl = 2.0 * cin_alg * cout_alg * KS * KS * px
-        if epi in (EPI_GDN, EPI_IGDN, EPI_GDN_BWD, EPI_IGDN_BWD):
-            fl += 2.0 * Cout * Cout * N * Ho * Wo
+        fl = None
+        if _flops:   # direct conv_ex calls only (bench.py takes the bmshj2018 layers' FLOPs from its own table)
+            px = N * (H * W if kind == 1 else Ho * Wo)
+            # alg_rows: real (non-padding) rows of a rho-ordered subpel weight (4 * C)
+            cin_alg = alg_rows if (fill_mode == FILL_UNSHUFFLE and alg_rows) else Cin
+            cout_alg = alg_rows if (ps and alg_rows) else Cout
+            fl = 2.0 * cin_alg * cout_alg * KS * KS * px
+            if epi in (EPI_GDN, EPI_IGDN, EPI_GDN_BWD, EPI_IGDN_BWD):
+                fl += 2.0 * Cout * Cout * N * Ho * Wo
         _ev_end(ev, fl)
     return y
 

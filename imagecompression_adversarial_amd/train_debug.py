@@ -51,8 +51,8 @@ def train_forward(ck, P, x4, noise_y=None, noise_z=None):
     zt4, zlik4, _ = K.eb_likelihood(z4, N, ck.eb, True, K.to_nc4(noise_z.contiguous()))
     hs = ck.hs.inner                     # MbtHyperSynthesis on the 16-channel z (h_s.0 weight zero-padded)
     M3 = hs.M3
-    s0, _, _ = K.conv_up(pad_nc4(zt4), CP, hs.convs[0].fwd, hs.convs[0].bias, M, K.EPI_LRELU, it=hs.convs[0].it_fwd)
-    s1, _, _ = K.conv_up(s0, M, hs.convs[1].fwd, hs.convs[1].bias, M3, K.EPI_LRELU, it=hs.convs[1].it_fwd)
+    s0, _, _ = K.conv_up(pad_nc4(zt4), CP, hs.convs[0].fwd, hs.convs[0].bias, M, K.EPI_LRELU)
+    s1, _, _ = K.conv_up(s0, M, hs.convs[1].fwd, hs.convs[1].bias, M3, K.EPI_LRELU)
     params4, _, _ = K.conv_down(s1, M3, hs.convs[2].fwd, hs.convs[2].bias, 2 * M, 3, 1, K.EPI_BIAS)
     c4 = (M + 3) // 4
     scales4, means4 = params4[:, :c4].contiguous(), params4[:, c4:].contiguous()

@@ -70,7 +70,7 @@ def synthesis_backward(ex, g4, y_in4, saved, params, grads, prefix):
         if i > 0:
             t = torch.empty_like(saved[i - 1][0])
             g, _, _ = K.conv_down(g, C, p.bwd, None, N, 5, 2, K.EPI_IGDN_BWD, ex.gdns[i - 1],
-                                  saved=saved[i - 1], save_t=t, it=p.it_bwd)
+                                  saved=saved[i - 1], save_t=t)
             q = f"{prefix}{2 * i - 1}"
             gdn_param_grads(params[f"{q}.beta"], params[f"{q}.gamma"], t, saved[i - 1], N, grads[f"{q}.beta"],
                             grads[f"{q}.gamma"])
@@ -94,13 +94,13 @@ def analysis_backward(ex, gy4, x4, saved, params, grads, prefix, input_grad=Fals
         if i > 0:
             t = torch.empty_like(saved[i - 1][0])
             g, _, _ = K.conv_up(g, C, ex.convs[i].bwd, None, N, K.EPI_GDN_BWD, ex.gdns[i - 1],
-                                saved=saved[i - 1], save_t=t, it=ex.convs[i].it_bwd)
+                                saved=saved[i - 1], save_t=t)
             q = f"{prefix}{2 * i - 1}"
             gdn_param_grads(params[f"{q}.beta"], params[f"{q}.gamma"], t, saved[i - 1], N, grads[f"{q}.beta"],
                             grads[f"{q}.gamma"])
         C = N
     if input_grad:
-        gx, _, _ = K.conv_up(g, N, ex.convs[0].bwd, None, 3, K.EPI_BIAS, prec=ex.convs[0].bwd_prec)
+        gx, _, _ = K.conv_up(g, N, ex.convs[0].bwd, None, 3, K.EPI_BIAS)
         return gx
     return None
 
@@ -221,8 +221,8 @@ class RDTrainer:
             if noise_z is None:
                 noise_z = torch.empty((B, N, H // 64, W // 64), device=x.device).uniform_(-0.5, 0.5)
             zt4, zlik4, _ = K.eb_likelihood(z4, N, ck.eb, True, K.to_nc4(noise_z.contiguous()))
-            s1, _, _ = K.conv_up(zt4, N, hs.convs[0].fwd, hs.convs[0].bias, N, K.EPI_RELU, it=hs.convs[0].it_fwd)
-            s2, _, _ = K.conv_up(s1, N, hs.convs[1].fwd, hs.convs[1].bias, N, K.EPI_RELU, it=hs.convs[1].it_fwd)
+            s1, _, _ = K.conv_up(zt4, N, hs.convs[0].fwd, hs.convs[0].bias, N, K.EPI_RELU)
+            s2, _, _ = K.conv_up(s1, N, hs.convs[1].fwd, hs.convs[1].bias, N, K.EPI_RELU)
             sig4, _, _ = K.conv_down(s2, N, hs.convs[2].fwd, hs.convs[2].bias, M, 3, 1, K.EPI_RELU)
             yt4, ylik4, _ = K.gc_likelihood(y4, M, sig4, None, True, ny4)
             liks = [ylik4, zlik4]
@@ -257,11 +257,11 @@ class RDTrainer:
             # h_a backward
             K.wgrad(gz, N, z2, N, 5, 2, self._g("h_a.4.weight"))
             K.channel_sum(gz, N, self._g("h_a.4.bias"))
-            g, _, _ = K.conv_up(gz, N, ha.convs[2].bwd, None, N, K.EPI_BIAS, it=ha.convs[2].it_bwd)
+            g, _, _ = K.conv_up(gz, N, ha.convs[2].bwd, None, N, K.EPI_BIAS)
             K.relu_bwd_(g, z2)
             K.wgrad(g, N, z1, N, 5, 2, self._g("h_a.2.weight"))
             K.channel_sum(g, N, self._g("h_a.2.bias"))
-            g, _, _ = K.conv_up(g, N, ha.convs[1].bwd, None, N, K.EPI_BIAS, it=ha.convs[1].it_bwd)
+            g, _, _ = K.conv_up(g, N, ha.convs[1].bwd, None, N, K.EPI_BIAS)
             K.relu_bwd_(g, z1)
             K.wgrad(g, N, a4, M, 3, 1, self._g("h_a.0.weight"))
             K.channel_sum(g, N, self._g("h_a.0.bias"))

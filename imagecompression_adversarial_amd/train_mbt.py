@@ -41,8 +41,8 @@ def train_forward(ck, P, x4, noise_y=None, noise_z=None):
     zt4, zlik4, _ = K.eb_likelihood(z4, N, ck.eb, True, K.to_nc4(noise_z.contiguous()))
     hs = ck.hs
     M3 = hs.M3
-    s0, _, _ = K.conv_up(zt4, N, hs.convs[0].fwd, hs.convs[0].bias, M, K.EPI_LRELU, it=hs.convs[0].it_fwd)
-    s1, _, _ = K.conv_up(s0, M, hs.convs[1].fwd, hs.convs[1].bias, M3, K.EPI_LRELU, it=hs.convs[1].it_fwd)
+    s0, _, _ = K.conv_up(zt4, N, hs.convs[0].fwd, hs.convs[0].bias, M, K.EPI_LRELU)
+    s1, _, _ = K.conv_up(s0, M, hs.convs[1].fwd, hs.convs[1].bias, M3, K.EPI_LRELU)
     params4, _, _ = K.conv_down(s1, M3, hs.convs[2].fwd, hs.convs[2].bias, 2 * M, 3, 1, K.EPI_BIAS)
     ent = entropy_forward(P, y4, M, params4, noise_y)
     xh4, ss = ck.gs.forward(ent["yh4"], save=True, split=False)
@@ -88,10 +88,10 @@ class MbtTrainStep(ChengTrainStep):
         # h_a backward: conv k5 s2 (N -> N), LReLU, conv k5 s2, LReLU, conv k3 (M -> N)
         ha, z0, z1 = f["ha"], f["z0"], f["z1"]
         self._wb(gz, N, z1, N, 5, 2, "h_a.4")
-        g, _, _ = K.conv_up(gz, N, ha[2].bwd, None, N, K.EPI_BIAS, it=ha[2].it_bwd)
+        g, _, _ = K.conv_up(gz, N, ha[2].bwd, None, N, K.EPI_BIAS)
         g = K.lrelu_bwd(g, z1)
         self._wb(g, N, z0, N, 5, 2, "h_a.2")
-        g, _, _ = K.conv_up(g, N, ha[1].bwd, None, N, K.EPI_BIAS, it=ha[1].it_bwd)
+        g, _, _ = K.conv_up(g, N, ha[1].bwd, None, N, K.EPI_BIAS)
         g = K.lrelu_bwd(g, z0)
         self._wb(g, N, f["y4"], M, 3, 1, "h_a.0")
         g, _, _ = K.conv_down(g, N, ha[0].bwd, None, M, 3, 1, K.EPI_BIAS)

@@ -197,21 +197,7 @@ typedef struct ica_ar_args {
 } ica_ar_args;
 size_t ica_ar_lds_bytes(int M, int E1, int E2);
 int ica_ar_step(const ica_ar_args* args, int p0, int p1, int mode, hipStream_t stream);
-/* y = conv2d(x, W, stride S, pad KS/2) (+ epilogue).  KS,S in {(5,2),(3,1)}.
- * GDN/IGDN: gp = gamma' fragments, beta = beta_eff, optional save_x/save_s outputs;
- * GDN_BWD/IGDN_BWD: x holds dL/d(conv output of the NEXT layer's input) ... i.e. acc = dL/dy of a GDN,
- * gp = gamma'^T fragments, in_x/in_s = the saved x/s of that GDN; y receives dL/dx. */
-int ica_conv_down(const float* x, float* y, const float* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                  int Cout, int Hout, int Wout, int KS, int S, int epi, const float* gp, const float* beta,
-                  float* save_x, float* save_s, const float* in_x, const float* in_s, float* save_t,
-                  hipStream_t stream);
-/* y = conv_transpose2d(x, W, stride 2, pad 2, output_padding 1) (+ epilogue); Cin % 16 == 0.
- * save_t (GDN_BWD/IGDN_BWD only, may be NULL): receives t = dL/dn, n = beta' + gamma' x^2 the GDN norm
- * (nChw4c), from which the GDN parameter gradients follow (ica_channel_sum, ica_wgrad KS=1). */
-int ica_conv_up(const float* x, float* y, const float* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                int Cout, int Hout, int Wout, int epi, const float* gp, const float* beta, float* save_x,
-                float* save_s, const float* in_x, const float* in_s, float* save_t, hipStream_t stream);
-/* Generic launch (all geometries / epilogues / extras).  kind 0 = conv_down (stride-S KSxKS conv, pad KS/2;
+/* The conv launch (all geometries / epilogues / extras).  kind 0 = conv_down (stride-S KSxKS conv, pad KS/2;
  * (KS,S) in {(5,2),(3,1),(3,2),(1,2),(1,1),(5,1)}), kind 1 = conv_up (stride-2 transposed conv, pad KS/2,
  * output_padding 1; KS in {5,3,1} — the input-gradient of a stride-2 conv).  Epilogues add ICA_EPI_LRELU (6,
  * slope 0.01) and ICA_EPI_LRELU_BWD (7: y = acc * (in_x > 0 ? 1 : 0.01)).  Optional extras:
@@ -220,8 +206,17 @@ int ica_conv_up(const float* x, float* y, const float* wp, const float* bias, in
  *   ps         PixelShuffle(2) store (rho-ordered rows: rho = 16*c4 + 4*q + e -> channel 4*c4+e, sub-pixel q)
  *   fill_mode  conv_down input view: 1 = x * leaky_relu'(mask), 2 = PixelUnshuffle(2) of a (2H)x(2W) x
  *   it         32-channel row tiles per wave (0 = ica_conv_it(Cout)); 6 runs C = 192 GDN layers in one wave.
+ * GDN / IGDN: gp = gamma' fragments, beta = beta_eff, optional save_s output (y = x * s is the layer's output).
+ * GDN_BWD / IGDN_BWD: x holds dL/dy of the GDN behind this conv's output, gp = gamma'^T fragments, in_x / in_s = that
+ * GDN's saved (y, s); y receives dL/dx.  save_t (may be NULL) receives t = dL/dn, n = beta' + gamma' x^2 the GDN
+ * norm, from which the GDN parameter gradients follow (ica_channel_sum, ica_wgrad KS=1).
  * Reference: CompressAI cheng2020-anchor blocks (anchors/model.py:76-77). */
 enum { ICA_EPI_LRELU = 6, ICA_EPI_LRELU_BWD = 7 };
+/* Fragment orders of a packed weight (ica_conv_args.order).  DOWN / UP: the `order` argument of the packers (conv_down
+ * [cb][chunk][tap], conv_up [cb][tap][chunk]); RGB5: the dense tap-row pack (order 2 of ica_pack_conv_weight_bf16 /
+ * _x6); TG: the tap groups ica_pack_conv_weight_bf16 writes for C <= 4 with order 0; UP3: the Z-gather pack of
+ * ica_pack_up3* (read by ica_conv_up3* only, never by ica_conv_ex). */
+enum { ICA_ORDER_DOWN = 0, ICA_ORDER_UP = 1, ICA_ORDER_RGB5 = 2, ICA_ORDER_TG = 3, ICA_ORDER_UP3 = 4 };
 typedef struct ica_conv_args {
   const float* x;
   float* y;
@@ -253,6 +248,9 @@ typedef struct ica_conv_args {
                * every other output-layout tensor (save_x / save_s, in_x / in_s, save_t, res).  A parity-split
                * H x W plane (H, W even) stores the four (y & 1, x & 1) sub-planes of (H/2) x (W/2) pixels one after
                * another, so a transposed conv's output-parity classes write and read dense lines */
+  int order; /* ICA_ORDER_* of wp.  Each route reads one order: kind 1 UP; kind 0 DOWN, but TG for prec 1 with Cin <= 4
+              * and RGB5 for the prec 1 / 2 RGB-side k5 s2 conv_down (Cin <= 3, 128 outputs, BIAS/GDN/IGDN_BWD, plain
+              * fill, no extras).  Any other order returns -4: a pack is never read as a layout it does not have */
 } ica_conv_args;
 int ica_conv_ex(const ica_conv_args* args, hipStream_t stream);
 /* Evidence, not compute: the kernel and grid of the calling thread's last kernel launch (any entry point of this

@@ -41,13 +41,13 @@ gflop = 2 * N * N * 256 * 384 * B               # the fused gamma' GEMM of a GDN
 # x6 MFMA cycles per launch summed over SIMDs: 6 bf16 32x32x16 MFMAs (32 cycles each) per 32x32x16 fp32-equivalent
 mfma_cycles = lambda fl: fl / (2 * 32 * 32 * 16) * 6 * 32   # noqa: E731
 cases = {
-    "down.bias (conv_down_x6w)": (lambda: K.conv_down(x_hi, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_BIAS, prec=wc.fwd_prec),
+    "down.bias (conv_down_x6w)": (lambda: K.conv_down(x_hi, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_BIAS),
                                   flop),
     "down.igdn_bwd (conv_down_x6w)": (lambda: K.conv_down(x_hi, N, wd.bwd, None, N, 5, 2, K.EPI_IGDN_BWD, gd,
-                                                          saved=(sx_lo, ss_lo), prec=wd.bwd_prec), flop + gflop // 4),
-    "up.bias (conv_up_x6w)": (lambda: K.conv_up(x_lo, N, wd.fwd, wd.bias, N, K.EPI_BIAS, prec=wd.fwd_prec), flop),
-    "up.gdn_bwd": (lambda: K.conv_up(x_lo, N, wc.bwd, None, N, K.EPI_GDN_BWD, gd, saved=(sx_hi, ss_hi),
-                                     prec=wc.bwd_prec), flop + gflop),
+                                                          saved=(sx_lo, ss_lo)), flop + gflop // 4),
+    "up.bias (conv_up_x6w)": (lambda: K.conv_up(x_lo, N, wd.fwd, wd.bias, N, K.EPI_BIAS), flop),
+    "up.gdn_bwd": (lambda: K.conv_up(x_lo, N, wc.bwd, None, N, K.EPI_GDN_BWD, gd, saved=(sx_hi, ss_hi)),
+                   flop + gflop),
 }
 if "--bf16" in sys.argv:   # config-5 shapes (8 x 2048^2: level 1 = 1024^2), bf16 kernels of ica_conv.hip (a
     # -DICA_CLOCK_STAMP build of ica_conv.hip; phases: class A main / epilogue, class B main / epilogue)
@@ -57,7 +57,7 @@ if "--bf16" in sys.argv:   # config-5 shapes (8 x 2048^2: level 1 = 1024^2), bf1
     y1b, s1b = K.empty_nc4(8, N, 1024, 1024, dev, BFT).uniform_(-1, 1), K.empty_nc4(8, N, 1024, 1024, dev, BFT).uniform_(0.5, 1)
     fl5 = 2 * N * N * 25 * 512 * 512 * 8
     cases = {"bf16 up.gdn_bwd 4w (config 5)": (lambda: K.conv_up(x2b, N, wcb.bwd, None, N, K.EPI_GDN_BWD, gd,
-                                                                  saved=(y1b, s1b), prec=1),
+                                                                  saved=(y1b, s1b)),
                                                fl5 + 2 * N * N * 1024 * 1024 * 8)}
     mfma_cycles = lambda fl: fl / (2 * 32 * 32 * 16) * 32   # noqa: E731  (one bf16 MFMA per 32x32x16)
 cases = {k: v for k, v in cases.items() if only in k}

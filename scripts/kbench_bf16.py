@@ -43,18 +43,17 @@ img[:, :, :, :, 3] = 0
 FL = 2.0 * N * N * 25 * 512 * 512 * B            # level-1 <-> level-2 conv
 FL0 = 2.0 * N * 3 * 25 * 1024 * 1024 * B         # RGB <-> level-1
 cases = {
-    "down_gdn   (g_a.2.fwd)": (lambda: K.conv_down(x1, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_GDN, gd, True, prec=1), FL),
-    "down_bias  (no GDN)": (lambda: K.conv_down(x1, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_BIAS, prec=1), FL),
+    "down_gdn   (g_a.2.fwd)": (lambda: K.conv_down(x1, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_GDN, gd, True), FL),
+    "down_bias  (no GDN)": (lambda: K.conv_down(x1, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_BIAS), FL),
     "down_igdnb (g_s.4.dgrad)": (lambda: K.conv_down(x1, N, wd.bwd, None, N, 5, 2, K.EPI_IGDN_BWD, gd,
-                                                      saved=(x2, s2), prec=1), FL),
-    "up_igdn    (g_s.4.fwd)": (lambda: K.conv_up(x2, N, wd.fwd, wd.bias, N, K.EPI_IGDN, gd, True, prec=1), FL),
-    "up_bias    (no GDN)": (lambda: K.conv_up(x2, N, wd.fwd, wd.bias, N, K.EPI_BIAS, prec=1), FL),
-    "up_gdnb    (g_a.2.dgrad)": (lambda: K.conv_up(x2, N, wc.bwd, None, N, K.EPI_GDN_BWD, gd, saved=(x1, s1),
-                                                    prec=1), FL),
-    "rgb_gdn    (g_a.0.fwd)": (lambda: K.conv_down(img, 3, w0.fwd, w0.bias, N, 5, 2, K.EPI_GDN, gd, True, prec=1), FL0),
+                                                      saved=(x2, s2)), FL),
+    "up_igdn    (g_s.4.fwd)": (lambda: K.conv_up(x2, N, wd.fwd, wd.bias, N, K.EPI_IGDN, gd, True), FL),
+    "up_bias    (no GDN)": (lambda: K.conv_up(x2, N, wd.fwd, wd.bias, N, K.EPI_BIAS), FL),
+    "up_gdnb    (g_a.2.dgrad)": (lambda: K.conv_up(x2, N, wc.bwd, None, N, K.EPI_GDN_BWD, gd, saved=(x1, s1)), FL),
+    "rgb_gdn    (g_a.0.fwd)": (lambda: K.conv_down(img, 3, w0.fwd, w0.bias, N, 5, 2, K.EPI_GDN, gd, True), FL0),
     "rgb_igdnb  (g_s.6.dgrad)": (lambda: K.conv_down(img, 3, w6.bwd, None, N, 5, 2, K.EPI_IGDN_BWD, gd,
-                                                      saved=(x1, s1), prec=1), FL0),
-    "up3        (g_s.6.fwd)": (lambda: K.conv_up(x1, N, w6.fwd, w6.bias, 3, prec=1), FL0),
+                                                      saved=(x1, s1)), FL0),
+    "up3        (g_s.6.fwd)": (lambda: K.conv_up(x1, N, w6.fwd, w6.bias, 3), FL0),
 }
 for name, (fn, fl) in cases.items():
     if ONLY and ONLY not in name:

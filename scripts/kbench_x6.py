@@ -44,16 +44,14 @@ cases = {}
 for pr, nm in ((K.PREC_FP32, "fp32"), (K.PREC_X6, "x6")):
     wc, wd = P[pr]
     cases.update({
-        f"{nm} down.bias": lambda wc=wc, pr=pr: K.conv_down(x_hi, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_BIAS, prec=wc.fwd_prec),
-        f"{nm} down.gdn(save)": lambda wc=wc: K.conv_down(x_hi, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_GDN, gd, save=True,
-                                                        prec=wc.fwd_prec),
+        f"{nm} down.bias": lambda wc=wc, pr=pr: K.conv_down(x_hi, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_BIAS),
+        f"{nm} down.gdn(save)": lambda wc=wc: K.conv_down(x_hi, N, wc.fwd, wc.bias, N, 5, 2, K.EPI_GDN, gd, save=True),
         f"{nm} down.igdn_bwd": lambda wd=wd: K.conv_down(x_hi, N, wd.bwd, None, N, 5, 2, K.EPI_IGDN_BWD, gd,
-                                                       saved=(sx_lo, ss_lo), prec=wd.bwd_prec),
-        f"{nm} up.bias": lambda wd=wd: K.conv_up(x_lo, N, wd.fwd, wd.bias, N, K.EPI_BIAS, prec=wd.fwd_prec),
-        f"{nm} up.igdn(save)": lambda wd=wd: K.conv_up(x_lo, N, wd.fwd, wd.bias, N, K.EPI_IGDN, gd, save=True,
-                                                     prec=wd.fwd_prec),
-        f"{nm} up.gdn_bwd": lambda wc=wc: K.conv_up(x_lo, N, wc.bwd, None, N, K.EPI_GDN_BWD, gd, saved=(sx_hi, ss_hi),
-                                                  prec=wc.bwd_prec),
+                                                       saved=(sx_lo, ss_lo)),
+        f"{nm} up.bias": lambda wd=wd: K.conv_up(x_lo, N, wd.fwd, wd.bias, N, K.EPI_BIAS),
+        f"{nm} up.igdn(save)": lambda wd=wd: K.conv_up(x_lo, N, wd.fwd, wd.bias, N, K.EPI_IGDN, gd, save=True),
+        f"{nm} up.gdn_bwd": lambda wc=wc: K.conv_up(x_lo, N, wc.bwd, None, N, K.EPI_GDN_BWD, gd,
+                                                  saved=(sx_hi, ss_hi)),
     })
 W3 = r(N, 3, 5, 5) * 0.1
 R = {pr: (K.PackedConv(W3, b, "conv", 2, pr), K.PackedConv(W3, None, "deconv", 2, pr)) for pr in (K.PREC_FP32, K.PREC_X6)}
@@ -62,14 +60,13 @@ flop_rgb = 2 * N * 3 * 25 * 256 * 384 * B
 for pr, nm in ((K.PREC_FP32, "fp32"), (K.PREC_X6, "x6")):
     rc, rd = R[pr]
     cases.update({
-        f"{nm} rgb.gdn(save)": lambda rc=rc: K.conv_down(x_rgb, 3, rc.fwd, rc.bias, N, 5, 2, K.EPI_GDN, gd, save=True,
-                                                       prec=rc.fwd_prec),
+        f"{nm} rgb.gdn(save)": lambda rc=rc: K.conv_down(x_rgb, 3, rc.fwd, rc.bias, N, 5, 2, K.EPI_GDN, gd, save=True),
         f"{nm} rgb.igdn_bwd": lambda rd=rd: K.conv_down(x_rgb, 3, rd.bwd, None, N, 5, 2, K.EPI_IGDN_BWD, gd,
-                                                      saved=(sx_hi, ss_hi), prec=rd.bwd_prec),
+                                                      saved=(sx_hi, ss_hi)),
     })
 U3 = {pr: K.PackedConv(W3, b[:3].contiguous(), "deconv", 2, pr) for pr in (K.PREC_FP32, K.PREC_X6)}
 for pr, nm in ((K.PREC_FP32, "fp32"), (K.PREC_X6, "x6")):
-    cases[f"{nm} up3.bias"] = lambda u=U3[pr]: K.conv_up(x_hi, N, u.fwd, u.bias, 3, K.EPI_BIAS, prec=u.fwd_prec)
+    cases[f"{nm} up3.bias"] = lambda u=U3[pr]: K.conv_up(x_hi, N, u.fwd, u.bias, 3, K.EPI_BIAS)
 cases = {k: f for k, f in cases.items() if only in k}
 times = {k: [] for k in cases}
 for rnd in range(6):

@@ -67,6 +67,31 @@ def test_bindings_match_header_prototypes():
         assert _ctype_class(_lib._RESTYPES.get(name, _lib._i)) == ret, name
 
 
+def test_conv_args_struct_matches_header():
+    """_lib.ConvArgs has the fields of include/ica_hip.h's ica_conv_args, in order and by class (pointer / int),
+    and hip_ops' ORDER_* are the header's ICA_ORDER_*."""
+    import ctypes as C
+    from imagecompression_adversarial_amd import _lib, hip_ops as K
+    txt = open(os.path.join(REPO, "include", "ica_hip.h")).read()
+    body = re.search(r"typedef struct ica_conv_args \{(.*?)\} ica_conv_args;", txt, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", " ", body, flags=re.S)
+    want = []
+    for decl in body.split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        typ, names = decl.rsplit(" ", 1)[0], decl
+        if "*" in decl:
+            want.append((decl.rsplit("*", 1)[1].strip(), C.c_void_p))
+        else:
+            assert typ.split()[0] == "int", decl
+            want += [(n.strip(), C.c_int) for n in names[len("int"):].split(",")]
+    assert [(n, t) for n, t in _lib.ConvArgs._fields_] == want
+    orders = dict(re.findall(r"ICA_ORDER_(\w+) = (\d+)", txt))
+    assert {k: int(v) for k, v in orders.items()} == {
+        "DOWN": K.ORDER_DOWN, "UP": K.ORDER_UP, "RGB5": K.ORDER_RGB5, "TG": K.ORDER_TG, "UP3": K.ORDER_UP3}
+
+
 def test_integration_snippet_matches_header():
     """The ctypes stub INTEGRATION.md shows a maintainer (`lib.<name>.argtypes = [...]`) declares each entry point
     exactly as include/ica_hip.h does."""

@@ -57,8 +57,8 @@ def test_conv_down_bf16(K, cin, cout, hw):
     emu = F.conv2d(bf(x), bf(w), b, stride=2, padding=2)
     ref = F.conv2d(x, w, b, stride=2, padding=2)
     p = K.PackedConv(w.to(DEV), b.to(DEV), "conv", 2, K.PREC_BF16)
-    assert p.fwd_prec == K.PREC_BF16 and p.fwd.dtype == torch.bfloat16
-    y4, _, _ = K.conv_down(nc4b(K, x), cin, p.fwd, p.bias, cout, 5, 2, K.EPI_BIAS, prec=p.fwd_prec)
+    assert p.fwd_prec == K.PREC_BF16 and p.fwd.data.dtype == torch.bfloat16
+    y4, _, _ = K.conv_down(nc4b(K, x), cin, p.fwd, p.bias, cout, 5, 2, K.EPI_BIAS)
     assert y4.dtype == torch.bfloat16
     y = unb(K, y4, cout)
     assert rel_err(y, emu) < 4e-3
@@ -74,7 +74,7 @@ def test_conv_up_bf16(K, cin, cout, hw):
     emu = F.conv_transpose2d(bf(x), bf(w), b, stride=2, padding=2, output_padding=1)
     p = K.PackedConv(w.to(DEV), b.to(DEV), "deconv", 2, K.PREC_BF16)
     assert p.fwd_prec == K.PREC_BF16
-    y4, _, _ = K.conv_up(nc4b(K, x), cin, p.fwd, p.bias, cout, prec=p.fwd_prec)
+    y4, _, _ = K.conv_up(nc4b(K, x), cin, p.fwd, p.bias, cout)
     assert rel_err(unb(K, y4, cout), emu) < 4e-3
 
 
@@ -100,12 +100,11 @@ def test_gdn_fwd_epilogues_bf16(K, inverse, C, cin):
     b = rnd((C,), 15) * 0.1
     if not inverse:
         p = K.PackedConv(w.to(DEV), b.to(DEV), "conv", 2, K.PREC_BF16, it_fwd=it)
-        y4, _, ss = K.conv_down(nc4b(K, x), cin, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gdn, True, prec=p.fwd_prec,
-                                it=it)
+        y4, _, ss = K.conv_down(nc4b(K, x), cin, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gdn, True)
         pre = F.conv2d(bf(x), bf(w), b, stride=2, padding=2)
     else:
         p = K.PackedConv(w.to(DEV), b.to(DEV), "deconv", 2, K.PREC_BF16, it_fwd=it)
-        y4, _, ss = K.conv_up(nc4b(K, x), cin, p.fwd, p.bias, C, K.EPI_IGDN, gdn, True, prec=p.fwd_prec, it=it)
+        y4, _, ss = K.conv_up(nc4b(K, x), cin, p.fwd, p.bias, C, K.EPI_IGDN, gdn, True)
         pre = F.conv_transpose2d(bf(x), bf(w), b, stride=2, padding=2, output_padding=1)
     out = codec.gdn(pre, beta, gamma, inverse)
     assert rel_err(unb(K, y4, C), out) < 4e-3
@@ -147,11 +146,9 @@ def test_gdn_bwd_epilogues_bf16(K, inverse, C, cg):
     saved = (nc4b(K, yprev.detach()), nc4b(K, s))
     assert p.bwd_prec == K.PREC_BF16
     if not inverse:
-        out4, _, _ = K.conv_up(nc4b(K, g), cg, p.bwd, None, C, K.EPI_GDN_BWD, gdn, saved=saved, prec=p.bwd_prec,
-                               it=it)
+        out4, _, _ = K.conv_up(nc4b(K, g), cg, p.bwd, None, C, K.EPI_GDN_BWD, gdn, saved=saved)
     else:
-        out4, _, _ = K.conv_down(nc4b(K, g), C, p.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gdn, saved=saved,
-                                 prec=p.bwd_prec, it=it)
+        out4, _, _ = K.conv_down(nc4b(K, g), C, p.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gdn, saved=saved)
     assert rel_err(unb(K, out4, C), ad.grad) < 1.5e-2
 
 
@@ -222,8 +219,7 @@ def test_rgb_input_conv_bf16_tap_groups(K, hw, C):
     gdn = K.PackedGDN(beta.to(DEV), gamma.to(DEV))
     p = K.PackedConv(w.to(DEV), b.to(DEV), "conv", 2, K.PREC_BF16, it_fwd=it)
     assert p.fwd_prec == K.PREC_BF16
-    y4, _, _ = K.conv_down(K.to_nc4(x.to(DEV)), 3, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gdn, True, prec=p.fwd_prec,
-                           it=it)
+    y4, _, _ = K.conv_down(K.to_nc4(x.to(DEV)), 3, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gdn, True)
     ref = codec.gdn(F.conv2d(bf(x), bf(w), b, stride=2, padding=2), beta, gamma, False)
     assert rel_err(unb(K, y4, C), ref) < 4e-3
 
@@ -240,7 +236,7 @@ def test_rgb_output_deconv_bf16(K, hw, C):
     b = rnd((3,), 53) * 0.1
     p = K.PackedConv(w.to(DEV), b.to(DEV), "deconv", 2, K.PREC_BF16, it_bwd=it)
     assert p.fwd_prec == K.PREC_BF16 and p.bwd_prec == K.PREC_BF16
-    y4, _, _ = K.conv_up(nc4b(K, x), C, p.fwd, p.bias, 3, prec=p.fwd_prec)
+    y4, _, _ = K.conv_up(nc4b(K, x), C, p.fwd, p.bias, 3)
     emu = F.conv_transpose2d(bf(x), bf(w), b, stride=2, padding=2, output_padding=1)
     assert rel_err(K.from_nc4(y4, 3).cpu(), emu) < 2e-5
     # input-gradient through the preceding IGDN
@@ -253,8 +249,7 @@ def test_rgb_output_deconv_bf16(K, hw, C):
     s = (yprev / a).detach()
     yprev.backward(F.conv2d(bf(g), bf(w), None, stride=2, padding=2))
     saved = (nc4b(K, yprev.detach()), nc4b(K, s))
-    out4, _, _ = K.conv_down(K.to_nc4(g.to(DEV)), 3, p.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gdn, saved=saved,
-                             prec=p.bwd_prec, it=it)
+    out4, _, _ = K.conv_down(K.to_nc4(g.to(DEV)), 3, p.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gdn, saved=saved)
     assert rel_err(unb(K, out4, C), ad.grad) < 1.5e-2
 
 
@@ -267,6 +262,6 @@ def test_first_conv_dgrad_bf16(K, hw):
     g = rnd((2, C, H, W), 62)
     p = K.PackedConv(w.to(DEV), None, "conv", 2, K.PREC_BF16)
     assert p.bwd_prec == K.PREC_BF16
-    out4, _, _ = K.conv_up(nc4b(K, g), C, p.bwd, None, 3, prec=p.bwd_prec)
+    out4, _, _ = K.conv_up(nc4b(K, g), C, p.bwd, None, 3)
     emu = F.conv_transpose2d(bf(g), bf(w), None, stride=2, padding=2, output_padding=1)
     assert rel_err(K.from_nc4(out4, 3).cpu(), emu) < 2e-5

@@ -53,7 +53,7 @@ def test_conv_up_lrelu(K, KS, Cin, Cout, H, W):
     b = rnd((Cout,), 41, -0.1, 0.1)
     x = rnd((2, Cin, H, W), 42)
     p = K.PackedConv(w.to(DEV), b.to(DEV), "deconv", 2, it_fwd=_up_it(Cout))
-    y4, _, _ = K.conv_up(K.to_nc4(x.to(DEV)), Cin, p.fwd, p.bias, Cout, K.EPI_LRELU, it=p.it_fwd)
+    y4, _, _ = K.conv_up(K.to_nc4(x.to(DEV)), Cin, p.fwd, p.bias, Cout, K.EPI_LRELU)
     ref = F.leaky_relu(F.conv_transpose2d(x, w, b, stride=2, padding=2, output_padding=1), 0.01)
     assert rel_err(K.from_nc4(y4, Cout).cpu(), ref) < 1e-4
 

@@ -57,19 +57,15 @@ def test_analysis_gdn_pair(K, hw, prec):
     p0 = K.PackedConv(w0.to(DEV), b0.to(DEV), "conv", 2, pr)
     p1 = K.PackedConv(w1.to(DEV), None, "conv", 2, pr)
     assert p0.fwd_prec == pr and p1.bwd_prec == pr
-    y4, sx, ss = K.conv_down(K.to_nc4(x0.to(DEV)), C, p0.fwd, p0.bias, C, 5, 2, K.EPI_GDN, gd, save=True,
-                             prec=p0.fwd_prec)
+    y4, sx, ss = K.conv_down(K.to_nc4(x0.to(DEV)), C, p0.fwd, p0.bias, C, 5, 2, K.EPI_GDN, gd, save=True)
     assert rel_err(K.from_nc4(y4, C).cpu(), y.detach()) < 2e-5
-    dx4, _, _ = K.conv_up(K.to_nc4(gz.to(DEV)), C, p1.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(sx, ss),
-                          prec=p1.bwd_prec)
+    dx4, _, _ = K.conv_up(K.to_nc4(gz.to(DEV)), C, p1.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(sx, ss))
     dx = K.from_nc4(dx4, C).cpu()
     assert rel_err(dx, pre.grad) < 5e-5
     # per-image kernel choice: image 1 alone gives the same bits as in the batch
-    y4b, sxb, ssb = K.conv_down(K.to_nc4(x0[1:].to(DEV)), C, p0.fwd, p0.bias, C, 5, 2, K.EPI_GDN, gd, save=True,
-                                prec=p0.fwd_prec)
+    y4b, sxb, ssb = K.conv_down(K.to_nc4(x0[1:].to(DEV)), C, p0.fwd, p0.bias, C, 5, 2, K.EPI_GDN, gd, save=True)
     assert torch.equal(y4b, y4[1:]) and torch.equal(ssb, ss[1:])
-    dx4b, _, _ = K.conv_up(K.to_nc4(gz[1:].to(DEV)), C, p1.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(sxb, ssb),
-                           prec=p1.bwd_prec)
+    dx4b, _, _ = K.conv_up(K.to_nc4(gz[1:].to(DEV)), C, p1.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(sxb, ssb))
     assert torch.equal(dx4b, dx4[1:])
 
 
@@ -86,14 +82,12 @@ def test_x6_down_pt1_same_bits(K, B, hw):
     w = rnd((C, C, 5, 5), 53) * 0.02
     b = rnd((C,), 54) * 0.1
     p = K.PackedConv(w.to(DEV), b.to(DEV), "conv", 2, K.PREC_X6)
-    y8, _, s8 = K.conv_down(K.to_nc4(x), C, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gd, save=True, prec=p.fwd_prec)
-    y1, _, s1 = K.conv_down(K.to_nc4(x[:1]), C, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gd, save=True, prec=p.fwd_prec)
+    y8, _, s8 = K.conv_down(K.to_nc4(x), C, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gd, save=True)
+    y1, _, s1 = K.conv_down(K.to_nc4(x[:1]), C, p.fwd, p.bias, C, 5, 2, K.EPI_GDN, gd, save=True)
     assert torch.equal(y1, y8[:1]) and torch.equal(s1, s8[:1])
     pd = K.PackedConv(w.to(DEV), None, "deconv", 2, K.PREC_X6)
-    g8, _, _ = K.conv_down(K.to_nc4(x), C, pd.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(y8, s8),
-                           prec=pd.bwd_prec)
-    g1, _, _ = K.conv_down(K.to_nc4(x[:1]), C, pd.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(y1, s1),
-                           prec=pd.bwd_prec)
+    g8, _, _ = K.conv_down(K.to_nc4(x), C, pd.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(y8, s8))
+    g1, _, _ = K.conv_down(K.to_nc4(x[:1]), C, pd.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(y1, s1))
     assert torch.equal(g1, g8[:1])
 
 
@@ -108,12 +102,12 @@ def test_x6_up_pt1_same_bits(K):
     wt = rnd((C, C, 5, 5), 63) * 0.02
     b = rnd((C,), 64) * 0.1
     pd = K.PackedConv(wt.to(DEV), b.to(DEV), "deconv", 2, K.PREC_X6)
-    yB, _, sB = K.conv_up(K.to_nc4(x), C, pd.fwd, pd.bias, C, K.EPI_IGDN, gd, save=True, prec=pd.fwd_prec)
-    y1, _, s1 = K.conv_up(K.to_nc4(x[:1]), C, pd.fwd, pd.bias, C, K.EPI_IGDN, gd, save=True, prec=pd.fwd_prec)
+    yB, _, sB = K.conv_up(K.to_nc4(x), C, pd.fwd, pd.bias, C, K.EPI_IGDN, gd, save=True)
+    y1, _, s1 = K.conv_up(K.to_nc4(x[:1]), C, pd.fwd, pd.bias, C, K.EPI_IGDN, gd, save=True)
     assert torch.equal(y1, yB[:1]) and torch.equal(s1, sB[:1])
     pc = K.PackedConv(wt.to(DEV), None, "conv", 2, K.PREC_X6)
-    gB, _, _ = K.conv_up(K.to_nc4(x), C, pc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(yB, sB), prec=pc.bwd_prec)
-    g1, _, _ = K.conv_up(K.to_nc4(x[:1]), C, pc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(y1, s1), prec=pc.bwd_prec)
+    gB, _, _ = K.conv_up(K.to_nc4(x), C, pc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(yB, sB))
+    g1, _, _ = K.conv_up(K.to_nc4(x[:1]), C, pc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(y1, s1))
     assert torch.equal(g1, gB[:1])
 
 
@@ -140,13 +134,11 @@ def test_synthesis_igdn_pair(K, hw, prec):
     p0 = K.PackedConv(w0.to(DEV), b0.to(DEV), "deconv", 2, pr)
     p1 = K.PackedConv(w1.to(DEV), None, "deconv", 2, pr)
     assert p0.fwd_prec == pr and p1.bwd_prec == pr
-    y4, sx, ss = K.conv_up(K.to_nc4(x0.to(DEV)), C, p0.fwd, p0.bias, C, K.EPI_IGDN, gd, save=True, prec=p0.fwd_prec)
+    y4, sx, ss = K.conv_up(K.to_nc4(x0.to(DEV)), C, p0.fwd, p0.bias, C, K.EPI_IGDN, gd, save=True)
     assert rel_err(K.from_nc4(y4, C).cpu(), y.detach()) < 2e-5
-    dx4, _, _ = K.conv_down(K.to_nc4(gz.to(DEV)), C, p1.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(sx, ss),
-                            prec=p1.bwd_prec)
+    dx4, _, _ = K.conv_down(K.to_nc4(gz.to(DEV)), C, p1.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(sx, ss))
     assert rel_err(K.from_nc4(dx4, C).cpu(), pre.grad) < 5e-5
-    y4b, sxb, ssb = K.conv_up(K.to_nc4(x0[:1].to(DEV)), C, p0.fwd, p0.bias, C, K.EPI_IGDN, gd, save=True,
-                              prec=p0.fwd_prec)
+    y4b, sxb, ssb = K.conv_up(K.to_nc4(x0[:1].to(DEV)), C, p0.fwd, p0.bias, C, K.EPI_IGDN, gd, save=True)
     assert torch.equal(y4b, y4[:1]) and torch.equal(ssb, ss[:1])
 
 
@@ -161,12 +153,12 @@ def test_bias_layers(K, cout, hw, prec):
     b = rnd((cout,), 43) * 0.1
     ref = F.conv2d(x, w, b, stride=2, padding=2)
     p = K.PackedConv(w.to(DEV), b.to(DEV), "conv", 2, K.PREC_X6 if prec == "x6" else K.PREC_FP32)
-    y4, _, _ = K.conv_down(K.to_nc4(x.to(DEV)), C, p.fwd, p.bias, cout, 5, 2, K.EPI_BIAS, prec=p.fwd_prec)
+    y4, _, _ = K.conv_down(K.to_nc4(x.to(DEV)), C, p.fwd, p.bias, cout, 5, 2, K.EPI_BIAS)
     assert rel_err(K.from_nc4(y4, cout).cpu(), ref) < 2e-5
     # input gradient (conv_up from cout channels back to C)
     xr = x.clone().requires_grad_(True)
     yr = F.conv2d(xr, w, None, stride=2, padding=2)
     g = rnd(tuple(yr.shape), 44)
     yr.backward(g)
-    gx4, _, _ = K.conv_up(K.to_nc4(g.to(DEV)), cout, p.bwd, None, C, prec=p.bwd_prec)
+    gx4, _, _ = K.conv_up(K.to_nc4(g.to(DEV)), cout, p.bwd, None, C)
     assert rel_err(K.from_nc4(gx4, C).cpu(), xr.grad) < 2e-5

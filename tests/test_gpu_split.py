@@ -69,19 +69,18 @@ def test_conv_down_split(B, Ho, Wo, lay_out):
     out = merge4 if lay_out else (lambda t: t)
     sv = split4 if lay_out else (lambda t: t)
     # bias
-    y0, _, _ = K.conv_down(x, C, conv.fwd, conv.bias, C, 5, 2, K.EPI_BIAS, prec=K.PREC_X6)
-    y1, _, _ = K.conv_down(split4(x), C, conv.fwd, conv.bias, C, 5, 2, K.EPI_BIAS, prec=K.PREC_X6, layout=lay)
+    y0, _, _ = K.conv_down(x, C, conv.fwd, conv.bias, C, 5, 2, K.EPI_BIAS)
+    y1, _, _ = K.conv_down(split4(x), C, conv.fwd, conv.bias, C, 5, 2, K.EPI_BIAS, layout=lay)
     _same(out(y1), y0)
     # GDN forward, saving s
-    y0, _, s0 = K.conv_down(x, C, conv.fwd, conv.bias, C, 5, 2, K.EPI_GDN, gd, True, prec=K.PREC_X6)
-    y1, _, s1 = K.conv_down(split4(x), C, conv.fwd, conv.bias, C, 5, 2, K.EPI_GDN, gd, True, prec=K.PREC_X6,
-                            layout=lay)
+    y0, _, s0 = K.conv_down(x, C, conv.fwd, conv.bias, C, 5, 2, K.EPI_GDN, gd, True)
+    y1, _, s1 = K.conv_down(split4(x), C, conv.fwd, conv.bias, C, 5, 2, K.EPI_GDN, gd, True, layout=lay)
     _same(out(y1), y0)
     _same(out(s1), s0)
     # IGDN backward (the g_s input gradient): saved (y, s) at the output level
-    y0, _, _ = K.conv_down(x, C, deconv.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(sy, ss), prec=K.PREC_X6)
+    y0, _, _ = K.conv_down(x, C, deconv.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(sy, ss))
     y1, _, _ = K.conv_down(split4(x), C, deconv.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(sv(sy), sv(ss)),
-                           prec=K.PREC_X6, layout=lay)
+                           layout=lay)
     _same(out(y1), y0)
 
 
@@ -105,16 +104,15 @@ def test_conv_up_split(B, H, W, Cin, lay_in):
     sy, ss = _act(B, C, 2 * H, 2 * W, 7, 0.0, 1.0), _act(B, C, 2 * H, 2 * W, 8, 0.5, 1.0)
     lay = K.LAYOUT_OUT | (K.LAYOUT_IN if lay_in else 0)
     xin = split4(x) if lay_in else x
-    y0, _, _ = K.conv_up(x, Cin, wd.fwd, wd.bias, C, K.EPI_BIAS, prec=K.PREC_X6)
-    y1, _, _ = K.conv_up(xin, Cin, wd.fwd, wd.bias, C, K.EPI_BIAS, prec=K.PREC_X6, layout=lay)
+    y0, _, _ = K.conv_up(x, Cin, wd.fwd, wd.bias, C, K.EPI_BIAS)
+    y1, _, _ = K.conv_up(xin, Cin, wd.fwd, wd.bias, C, K.EPI_BIAS, layout=lay)
     _same(merge4(y1), y0)
-    y0, _, s0 = K.conv_up(x, Cin, wd.fwd, wd.bias, C, K.EPI_IGDN, gd, True, prec=K.PREC_X6)
-    y1, _, s1 = K.conv_up(xin, Cin, wd.fwd, wd.bias, C, K.EPI_IGDN, gd, True, prec=K.PREC_X6, layout=lay)
+    y0, _, s0 = K.conv_up(x, Cin, wd.fwd, wd.bias, C, K.EPI_IGDN, gd, True)
+    y1, _, s1 = K.conv_up(xin, Cin, wd.fwd, wd.bias, C, K.EPI_IGDN, gd, True, layout=lay)
     _same(merge4(y1), y0)
     _same(merge4(s1), s0)
-    y0, _, _ = K.conv_up(x, Cin, wc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(sy, ss), prec=K.PREC_X6)
-    y1, _, _ = K.conv_up(xin, Cin, wc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(split4(sy), split4(ss)),
-                         prec=K.PREC_X6, layout=lay)
+    y0, _, _ = K.conv_up(x, Cin, wc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(sy, ss))
+    y1, _, _ = K.conv_up(xin, Cin, wc.bwd, None, C, K.EPI_GDN_BWD, gd, saved=(split4(sy), split4(ss)), layout=lay)
     _same(merge4(y1), y0)
 
 
@@ -126,20 +124,19 @@ def test_rgb_ends_split(B, H, W):
     gd, _, _, rgb, rgbd = _layers()
     C = 128
     x = _act(B, 3, H, W, 9, 0.0, 1.0)
-    y0, _, s0 = K.conv_down(x, 3, rgb.fwd, rgb.bias, C, 5, 2, K.EPI_GDN, gd, True, prec=K.PREC_X6)
-    y1, _, s1 = K.conv_down(x, 3, rgb.fwd, rgb.bias, C, 5, 2, K.EPI_GDN, gd, True, prec=K.PREC_X6,
-                            layout=K.LAYOUT_OUT)
+    y0, _, s0 = K.conv_down(x, 3, rgb.fwd, rgb.bias, C, 5, 2, K.EPI_GDN, gd, True)
+    y1, _, s1 = K.conv_down(x, 3, rgb.fwd, rgb.bias, C, 5, 2, K.EPI_GDN, gd, True, layout=K.LAYOUT_OUT)
     _same(merge4(y1), y0)
     _same(merge4(s1), s0)
     sy, ss = _act(B, C, H // 2, W // 2, 10, 0.0, 1.0), _act(B, C, H // 2, W // 2, 11, 0.5, 1.0)
-    g0, _, _ = K.conv_down(x, 3, rgbd.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(sy, ss), prec=K.PREC_X6)
+    g0, _, _ = K.conv_down(x, 3, rgbd.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(sy, ss))
     g1, _, _ = K.conv_down(x, 3, rgbd.bwd, None, C, 5, 2, K.EPI_IGDN_BWD, gd, saved=(split4(sy), split4(ss)),
-                           prec=K.PREC_X6, layout=K.LAYOUT_OUT)
+                           layout=K.LAYOUT_OUT)
     _same(merge4(g1), g0)
     h = _act(B, C, H // 2, W // 2, 12)
     for wp, bias in ((rgbd.fwd, rgbd.bias), (rgb.bwd, None)):
-        o0, _, _ = K.conv_up(h, C, wp, bias, 3, K.EPI_BIAS, prec=K.PREC_X6)
-        o1, _, _ = K.conv_up(split4(h), C, wp, bias, 3, K.EPI_BIAS, prec=K.PREC_X6, layout=K.LAYOUT_IN)
+        o0, _, _ = K.conv_up(h, C, wp, bias, 3, K.EPI_BIAS)
+        o1, _, _ = K.conv_up(split4(h), C, wp, bias, 3, K.EPI_BIAS, layout=K.LAYOUT_IN)
         _same(o1, o0)
 
 
@@ -157,7 +154,7 @@ def test_split_rejected_outside_k5s2():
     for prec in (K.PREC_FP32, K.PREC_X6):
         p5 = K.PackedConv(w5, None, "conv", 2, prec)
         with pytest.raises(RuntimeError):   # 17 x 17 output: an odd plane cannot be split
-            K.conv_down(_act(1, 128, 34, 34, 15), 128, p5.fwd, None, 128, 5, 2, K.EPI_BIAS, prec=p5.fwd_prec,
+            K.conv_down(_act(1, 128, 34, 34, 15), 128, p5.fwd, None, 128, 5, 2, K.EPI_BIAS,
                         layout=K.LAYOUT_OUT)
 
 
