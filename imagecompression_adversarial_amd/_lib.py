@@ -82,6 +82,11 @@ _SIGS = {
     "ica_bitdepth_noise_bwd": [_p, _p, _l, _f, _p],
     "ica_add": [_p, _p, _p, _l, _p],
     "ica_ensemble_grad": [_p, _p, _p, _l, _f, _p],
+    # latent range profile, clamp defence and detector (ica_latent.hip)
+    "ica_latent_range": [_p, _i, _i, _i, _i, _p, _p, _p, _p],
+    "ica_latent_clamp": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
+    "ica_latent_clamp_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "ica_latent_detect": [_p, _p, _p, _p, _p, _i, _i, _p],
     "ica_gc_symbols": [_p, _p, _p, _p, _i, _f, _p, _p, _i, _i, _i, _i, _p],
     "ica_eb_symbols": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ica_dequantize": [_p, _p, _p, _p, _i, _i, _i, _i, _p],

@@ -294,14 +294,22 @@ class CodecKernels:
         """y_hat into g_s: bf16 activations on the bf16 path (rounded latents are exact in bf16 up to 256)."""
         return K.cast_nc4(yh4, torch.bfloat16) if self.precision == "bf16" else yh4
 
-    def forward(self, x4, training=False, noise_y4=None, noise_z4=None):
-        """net(x) (anchors/balle.py:25-55): x_hat4, y4, likelihood tensors and per-image sum log p."""
+    def forward(self, x4, training=False, noise_y4=None, noise_z4=None, latent=None):
+        """net(x) (anchors/balle.py:25-55): x_hat4, y4, likelihood tensors and per-image sum log p.
+        latent (a function of the fp32 y4, e.g. the range clamp) gives the reference's defended eval
+        (attack_rd.py:263-268): y = latent(g_a(x)), likelihoods = entropy_estimator(y), x_hat = g_s(round(y));
+        the result's "y4" is the transformed latent.  Without it the launches are the plain forward's."""
         y4, _ = self.ga.forward(x4)
         if self.precision == "bf16":   # the entropy models and h_a run fp32
             y4 = K.cast_nc4(y4, torch.float32)
+        if latent is not None:
+            if training:
+                raise NotImplementedError("a latent transform is defined for the eval forward")
+            y4 = latent(y4)
         if self.model == "factorized":
             yh, ylik, ysum = K.eb_likelihood(y4, self.M, self.eb, training, noise_y4)
-            xh, _ = self.gs.forward(self._to_gs(yh))
+            # attack_rd.py:267 decodes round(y), not the bottleneck's round(y - median) + median
+            xh, _ = self.gs.forward(self._to_gs(yh if latent is None else K.round_(y4)))
             return {"x_hat4": xh, "y4": y4, "y_hat4": yh, "lik4": {"y": ylik}, "sumlog": ysum}
         if self.model == "context":
             return self._forward_context(y4, training)

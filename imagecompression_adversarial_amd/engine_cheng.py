@@ -417,12 +417,15 @@ class ChengKernels:
     def g_s_backward(self, gx4, saved):
         return self.gs.backward(gx4, saved)
 
-    def forward(self, x4, training=False, noise_y4=None, noise_z4=None):
-        """entropy_estimator (anchors/model.py:97-106) + g_s(y_hat), eval mode."""
+    def forward(self, x4, training=False, noise_y4=None, noise_z4=None, latent=None):
+        """entropy_estimator (anchors/model.py:97-106) + g_s(y_hat), eval mode.  latent: as CodecKernels.forward
+        (the defended eval of attack_rd.py:263-268; y_hat is round(y) here either way)."""
         if training:
             raise NotImplementedError("cheng2020 runs eval-mode forwards only (attack path)")
         N = self.N
         y4, _ = self.ga.forward(x4)
+        if latent is not None:   # on fp32, as CodecKernels.forward (every cheng2020 precision stores y4 in fp32 today)
+            y4 = latent(K.cast_nc4(y4, torch.float32))
         z4 = self.ha.forward(y4)
         zh, zlik, zsum = K.eb_likelihood(z4, N, self.eb, False, None)
         params = self.hs.forward(zh)

@@ -113,11 +113,13 @@ class DebugKernels:
     def g_s_backward(self, gx4, saved):
         return self.gs.backward(gx4, saved)
 
-    def forward(self, x4, training=False, noise_y4=None, noise_z4=None):
+    def forward(self, x4, training=False, noise_y4=None, noise_z4=None, latent=None):
         """ae_onelayer.forward (anchors/model.py:21-33), eval mode: likelihoods of the mean-scale hyperprior and
         x_hat = g_s(y)."""
         if training:
             raise NotImplementedError("ae_onelayer runs eval-mode forwards only (attack path)")
+        if latent is not None:
+            raise NotImplementedError("the latent-range defence is not defined for the debug model")
         y4, _ = self.ga.forward(x4)
         z4 = self.ha.forward(y4)
         zh, zlik, zsum = K.eb_likelihood(z4, self.N, self.eb, False, None)

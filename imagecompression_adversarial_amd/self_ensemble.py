@@ -12,6 +12,9 @@ defend              self_ensemble.py:156-171
 evaluate_defend     self_ensemble.py:173-252 (eval with args.defend)
 attack_/main        self_ensemble.py:275-444 (the L2 attack loop == attack.attack_batch, then eval with defend)
 DefendedAttackLoop  self_ensemble.py:253-326 with --adv: the attack through defend() (ensemble / bitdepth / resize)
+range (extension)   --defend_m range: the latent-range clamp of attack_rd.py:263-268 (clamp_value_naive) as a fourth
+                    defence of this eval, and the attack through it (latent_range.py, ica_latent.hip); the
+                    profile comes from --range-file (default: the reference's ./attack/data/..._range.pt)
 
 Reference semantics kept as they are (SURVEY Appendix B style):
   * ensemble: eval re-runs net(best_x) and compares its reconstruction, in the transformed frame of the
@@ -36,6 +39,7 @@ from . import hip_ops as K
 from . import msssim as MS
 from ._lib import call, ptr, stream
 from .attack import AttackLoop, attack_batch, eval_forward, evaluate
+from .latent_range import RangeProfile, latent_clamp, latent_clamp_bwd_
 
 RESIZE_SCALE = 243.0 / 256.0  # self_ensemble.py:160 random_resize(x, scale=243/256, random=False)
 
@@ -205,36 +209,65 @@ def defend(kern, x, method="ensemble"):
     return random_resize(x, scale=RESIZE_SCALE, random=False)[0]
 
 
-def evaluate_defend(kern, im_adv, im_s, output_s, method="ensemble", clamp=True, adv=False, msssim=True):
-    """self_ensemble.eval with args.defend (self_ensemble.py:173-252), per image.  Returns a list of dicts
-    {bpp, mse_in, mse_out, vi, vi_msim[, mse_pre, vi_pre][, best_idx]} and the defended outputs."""
-    B = im_adv.shape[0]
-    im_ = K.clamp01(im_adv) if clamp else im_adv
-    mse_in = K.sqdiff_mean(im_, im_s)
-    extra = [{} for _ in range(B)]
-    if method == "ensemble":
-        _, best_x, best_idx = self_ensemble(kern, im_)
-        xs = best_x
-        for b in range(B):
-            extra[b]["best_idx"] = best_idx[b]
-    else:
-        xp = defend(kern, im_, method)
-        if xp.shape != im_s.shape:
-            raise RuntimeError(f"defend '{method}' changed the image size {tuple(im_s.shape)} -> {tuple(xp.shape)}"
-                               " (the reference's mse_pre fails the same way)")
-        mse_pre = K.sqdiff_mean(im_s, xp)
-        xs = [xp[b:b + 1] for b in range(B)]
+def _eval_range(kern, im_, profile):
+    """attack_rd.py:263-268: y = clamp_value_naive(g_a(im_)), likelihoods = entropy_estimator(y),
+    output_ = clamp(g_s(round(y)), 0, 1) (whatever --clamp says).  Returns (output_, bpp[B], nclamped list)."""
+    if profile is None:
+        raise ValueError("method 'range' needs a RangeProfile (profile=...)")
+    B, _, H, W = im_.shape
+    counts = []
+
+    def clamp_latent(y4):
+        o, n = latent_clamp(y4, kern.M, profile, count=True)
+        counts.append(n)
+        return o
+
+    res = kern.forward(K.to_nc4(im_), latent=clamp_latent)
+    out = torch.empty_like(im_)
+    call("ica_nc4_bound_to_nchw", ptr(res["x_hat4"]), ptr(out), B, H, W, 1, stream())
+    return out, K.bits_to_bpp(res["sumlog"], H * W), counts[0].tolist()
+
+
+def _eval_preprocessed(kern, xs, output_s, clamp):
+    """The eval forward of each image's preprocessed input (ensemble / resize / bitdepth): (output_, bpp[B])."""
     outs, bpps = [], []
-    for b in range(B):
-        x = xs[b]
+    for x in xs:
         if x.shape[2:] != output_s.shape[2:]:
             raise RuntimeError("defended reconstruction and output_s differ in shape (rotated best variant of a "
                                "non-square image; the reference's mse_out fails the same way)")
         out, bpp = eval_forward(kern, x, clamp)
         outs.append(out)
         bpps.append(bpp)
-    output_ = torch.cat(outs, 0)
-    bpp = torch.cat(bpps, 0)
+    return torch.cat(outs, 0), torch.cat(bpps, 0)
+
+
+def evaluate_defend(kern, im_adv, im_s, output_s, method="ensemble", clamp=True, adv=False, msssim=True,
+                    profile=None):
+    """self_ensemble.eval with args.defend (self_ensemble.py:173-252), per image.  Returns a list of dicts
+    {bpp, mse_in, mse_out, vi, vi_msim[, mse_pre, vi_pre][, best_idx][, nclamped]} and the defended outputs.
+    method 'range' (profile: a latent_range.RangeProfile) is attack_rd.py's defended eval: nothing preprocesses
+    the image (no mse_pre / vi_pre); nclamped counts the latent elements the clamp changed."""
+    B = im_adv.shape[0]
+    im_ = K.clamp01(im_adv) if clamp else im_adv
+    mse_in = K.sqdiff_mean(im_, im_s)
+    extra = [{} for _ in range(B)]
+    if method == "range":
+        output_, bpp, ncl = _eval_range(kern, im_.contiguous(), profile)
+        for b in range(B):
+            extra[b]["nclamped"] = ncl[b]
+    else:
+        if method == "ensemble":
+            _, xs, best_idx = self_ensemble(kern, im_)
+            for b in range(B):
+                extra[b]["best_idx"] = best_idx[b]
+        else:
+            xp = defend(kern, im_, method)
+            if xp.shape != im_s.shape:
+                raise RuntimeError(f"defend '{method}' changed the image size {tuple(im_s.shape)} -> "
+                                   f"{tuple(xp.shape)} (the reference's mse_pre fails the same way)")
+            mse_pre = K.sqdiff_mean(im_s, xp)
+            xs = [xp[b:b + 1] for b in range(B)]
+        output_, bpp = _eval_preprocessed(kern, xs, output_s, clamp)
     mse_out = K.sqdiff_mean(output_, output_s)
     msim_in = msim_out = None
     if msssim:
@@ -346,12 +379,22 @@ class DefendedAttackLoop(AttackLoop):
                  for every model), the usual bounded L2 output loss.
       resize   : x_ = up(down(x)) (antialiased bicubic 243/256), x_hat = g_s(g_a(x_) + u_y); gradient through the
                  transposed resample passes.
+      range    : (no such loop in the reference; in the spirit of its --adv) x_hat = g_s(clamp(g_a(im_in))) on the
+                 unquantised latent, attack_our with clamp_value_naive between the transforms; the gradient goes
+                 g_s backward -> the clamp's where-masks (ica_latent_clamp_bwd) -> g_a backward.  No noise draw:
+                 deterministic.  fp32 / x6 operands.
     noise_fn(step, name, shape) may supply the uniform draws ("x": bit-depth noise, "y": latent noise); default:
     torch's device generator, U(-0.5, 0.5) as the reference draws them."""
 
-    def __init__(self, kern, im_s, method="ensemble", noise_fn=None, **kw):
-        if method not in ("ensemble", "resize", "bitdepth"):
-            raise ValueError(f"{method} not in 'ensemble', 'resize', 'bitdepth'")
+    def __init__(self, kern, im_s, method="ensemble", noise_fn=None, profile=None, **kw):
+        if method not in ("ensemble", "resize", "bitdepth", "range"):
+            raise ValueError(f"{method} not in 'ensemble', 'resize', 'bitdepth', 'range'")
+        if method == "range":
+            if getattr(kern, "precision", "fp32") == "bf16":
+                raise NotImplementedError("the attack through the latent clamp runs fp32 / x6 operands, not bf16")
+            if profile is None:
+                raise ValueError("method 'range' needs a RangeProfile (profile=...)")
+        self.profile = profile
         if kw.get("att_metric", "L2") != "L2" or kw.get("target") is not None or kw.get("coupled"):
             raise NotImplementedError("self_ensemble's attack is the per-image L2 attack")
         super().__init__(kern, im_s, **kw)
@@ -375,7 +418,18 @@ class DefendedAttackLoop(AttackLoop):
         assert idx is None, "DefendedAttackLoop runs the network on the full batch"
         if self.method == "ensemble":
             return self._grad_ensemble()
+        if self.method == "range":
+            return self._grad_range()
         return self._grad_noisy()
+
+    def _grad_range(self):
+        kern, B, H, W = self.kern, self.B, self.H, self.W
+        y4, sa = kern.g_a(self.im_in4, save=True)
+        xh4, ss = kern.g_s(latent_clamp(y4, kern.M, self.profile), save=True)
+        call("ica_attack_loss", ptr(xh4), ptr(self.output_s), ptr(self.grad4), ptr(self.part), B, H, W,
+             self.gscale, int(self.clamp), 0, stream())
+        gy4 = latent_clamp_bwd_(kern.g_s_backward(self.grad4, ss), y4, kern.M, self.profile)
+        return kern.g_a_backward(gy4, sa)
 
     def _grad_noisy(self):
         kern, B, H, W = self.kern, self.B, self.H, self.W
@@ -438,15 +492,15 @@ class DefendedAttackLoop(AttackLoop):
 
 
 def adv_attack_batch(kern, im_s, method="ensemble", steps=1001, epsilon=16.0, noise_thr=1e-4, lr=0.01, clamp=True,
-                     noise_fn=None, defend_eval=False, eval_msssim=True, record=False):
+                     noise_fn=None, defend_eval=False, eval_msssim=True, record=False, profile=None):
     """self_ensemble.attack_ with --adv (per image), then its eval (with --defend when defend_eval).
     Returns (AttackResult-like dict of the eval, the loop)."""
-    loop = DefendedAttackLoop(kern, im_s, method, noise_fn, steps=steps, epsilon=epsilon, noise_thr=noise_thr,
-                              lr=lr, clamp=clamp)
+    loop = DefendedAttackLoop(kern, im_s, method, noise_fn, profile, steps=steps, epsilon=epsilon,
+                              noise_thr=noise_thr, lr=lr, clamp=clamp)
     branches = loop.run(record=record)
     if defend_eval:
         res, out = evaluate_defend(kern, loop.im_in, loop.im_s, loop.output_s, method, clamp, adv=True,
-                                   msssim=eval_msssim)
+                                   msssim=eval_msssim, profile=profile)
     else:
         im_, out, bpp, mse_in, mse_out, msim_in, msim_out, vi, vi_msim = evaluate(
             kern, loop.im_in, loop.im_s, loop.output_s, clamp, adv=True, msssim=eval_msssim)
@@ -475,6 +529,9 @@ def batch_attack(args):
         p.requires_grad_(False)
     kern = net.kernels(net.attack_precision(getattr(args, "precision", None)))
     pre = args.method in ("resize", "bitdepth")
+    profile = None
+    if args.method == "range" and (args.defend or args.adv):
+        profile = RangeProfile.load(getattr(args, "range_file", None) or RangeProfile.default_path(args), args.device)
     bpp_ori_, bpp_, vi_, vi_pre_, n = 0.0, 0.0, 0.0, 0.0, 0
     for name, t, _, _ in _sources(args.source):
         start = time.time()
@@ -482,7 +539,8 @@ def batch_attack(args):
         if args.adv:   # attack through defend(net, im_in, args.method) (self_ensemble.py:259-262)
             rs, _, loop, _ = adv_attack_batch(kern, im_s, args.method, steps=args.steps, epsilon=args.epsilon,
                                               noise_thr=args.noise, lr=args.lr_attack, clamp=args.clamp,
-                                              defend_eval=args.defend, eval_msssim=min(im_s.shape[2:]) > 160)
+                                              defend_eval=args.defend, eval_msssim=min(im_s.shape[2:]) > 160,
+                                              profile=profile)
             r = rs[0]
             bpp, vi = r["bpp"], r["vi"]
             if args.defend and pre:
@@ -498,7 +556,7 @@ def batch_attack(args):
                            lr=args.lr_attack, clamp=args.clamp, eval_msssim=False)
         if args.defend:
             r = evaluate_defend(kern, res.im_adv, im_s, res.output_s, args.method, args.clamp,
-                                msssim=min(im_s.shape[2:]) > 160)[0][0]
+                                msssim=min(im_s.shape[2:]) > 160, profile=profile)[0][0]
             bpp, vi = r["bpp"], r["vi"]
             if pre:
                 vi_pre_ += r["vi_pre"] if r["vi_pre"] is not None else 0.0
@@ -519,8 +577,17 @@ def batch_attack(args):
     return {"bpp_ori": bpp_ori, "bpp": bpp, "vi": vi}
 
 
+def config():
+    """coder.config() plus this CLI's own flag (the way the reference's transfer_noise.py extends the parser)."""
+    p = coder.config()
+    p.add_argument("--range-file", dest="range_file", type=str, default=None,
+                   help="--defend_m range: the latent-range profile ([channel_max, channel_min], feature_range's "
+                        "output); default ./attack/data/{model}-{metric}-{quality}[-adv]_range.pt")
+    return p
+
+
 def main(argv=None):
-    args = coder.config().parse_args(argv)
+    args = config().parse_args(argv)
     return batch_attack(args)
 
 

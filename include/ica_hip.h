@@ -364,6 +364,31 @@ int ica_cw_round(const float* loss_i, const float* mse_o, double* sd, float* lol
  * here (every block of the image reads it); the next ica_cw_round rewrites it. */
 int ica_cw_reset(float* noise, float* m, float* v, const int* si, int B, long floats_per_image, hipStream_t stream);
 
+/* ---- latent range profile, clamp defence and detector (ica_latent.hip) ------
+ * The per-channel range of the latent y = g_a(x), the paper's "safe zone".  y4 / out4 / g4 are fp32 nChw4c
+ * [B][C/4][H][W][4]; cmax / cmin are the profile's channel_max / channel_min, float [C].  Every entry returns -2
+ * unless C is a multiple of 4, allocates nothing and runs on `stream`. */
+/* feature_range.py:19-21: out_max / out_min / out_absmax [B][C] = amax / amin / amax(abs) of each (image, channel)
+ * plane, the bits of torch.amax / torch.amin (a NaN in a plane gives NaN); out_absmax may be NULL.  One caveat: where
+ * the extreme of a plane is zero and the plane holds zeros of both signs, the sign of the returned zero is the
+ * hardware max / min's choice, which torch's CPU reduction (whose choice depends on its vector order) need not
+ * share; the value is equal either way. */
+int ica_latent_range(const float* y4, int B, int C, int H, int W, float* out_max, float* out_min, float* out_absmax,
+                     hipStream_t stream);
+/* clamp_value_naive (attack_rd.py:53-73, search.py:25-36): t = y > cmax ? cmax : y; out = t < cmin ? cmin : t
+ * (torch.where twice: a NaN passes through).  out4 may be y4.  nclamped (int [B], may be NULL) is zeroed and then
+ * counts the elements of each image with out != y. */
+int ica_latent_clamp(const float* y4, const float* cmax, const float* cmin, float* out4, int B, int C, int H, int W,
+                     int* nclamped, hipStream_t stream);
+/* The autograd of those two selects with respect to y, in place on g4: g where !(y > cmax) && !(t < cmin), else 0. */
+int ica_latent_clamp_bwd(float* g4, const float* y4, const float* cmax, const float* cmin, int B, int C, int H, int W,
+                         hipStream_t stream);
+/* detect (search.py:137-146) per image, from the image's channel extremes imax / imin [B][C]:
+ * score[b] = max_c(clamp(imax - cmax, min=0) / (cmax + 1)) + max_c|clamp(imin - cmin, max=0) / (cmin + 1)|, each
+ * step one correctly rounded fp32 operation, NaN propagating as in torch.max. */
+int ica_latent_detect(const float* imax, const float* imin, const float* cmax, const float* cmin, float* score, int B,
+                      int C, hipStream_t stream);
+
 /* ---- MS-SSIM (ica_msssim.hip) ---------------------------------------------- */
 /* mode 0 = pytorch_msssim (valid, per-channel, relu), mode 1 = utils/torch_msssim (same-pad, global). */
 int ica_msssim_blocks(int H, int W, int ws, int mode);
