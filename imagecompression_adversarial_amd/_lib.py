@@ -87,6 +87,10 @@ _SIGS = {
     "ica_latent_clamp": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     "ica_latent_clamp_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ica_latent_detect": [_p, _p, _p, _p, _p, _i, _i, _p],
+    # patch-wise VI localisation (ica_patch.hip)
+    "ica_patch_vi_ws_size": [_i, _i, _i, _i, _i],
+    "ica_patch_vi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "ica_patch_gather": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ica_gc_symbols": [_p, _p, _p, _p, _i, _f, _p, _p, _i, _i, _i, _i, _p],
     "ica_eb_symbols": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ica_dequantize": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
@@ -130,7 +134,7 @@ _SIGS = {
 }
 _RESTYPES = {"ica_pack_conv_weight_size": _sz, "ica_pack_conv_weight_bf16_size": _sz,
              "ica_pack_conv_weight_x6_size": _sz, "ica_pack_gdn_x6_size": _sz, "ica_pack_up3k3_x6_size": _sz, "ica_pack_up3_size": _sz, "ica_wgrad_ws_size": _sz,
-             "ica_rans_encode": _l, "ica_ar_lds_bytes": _sz}
+             "ica_rans_encode": _l, "ica_ar_lds_bytes": _sz, "ica_patch_vi_ws_size": _sz}
 
 
 

@@ -135,8 +135,9 @@ class attacker:
             p.requires_grad_(False)  # attack: input gradients only (reference computes unused wgrad)
         self.model_config = f"{args.model}_{args.quality}_{args.metric}_"
 
-    def attack(self, items):
-        """items: list of (name, tensor|None, H, W) of one image size; returns per-image results."""
+    def run(self, items):
+        """Load ``items`` (list of (name, tensor|None, H, W) of one image size) and attack them as one batch:
+        returns (ims, im_s, im_adv, output_adv, output_s, bpp_ori, bpp, mse, vi), the last four per image."""
         ims = []
         for name, t, H, W in items:
             if t is None:
@@ -146,6 +147,11 @@ class attacker:
         im_adv, output_adv, output_s, bpp_ori, bpp, mse, vi = attack_(im_s, self.net, self.args)
         if im_s.shape[0] == 1:
             bpp_ori, bpp, mse, vi = [bpp_ori], [bpp], [mse], [vi]
+        return ims, im_s, im_adv, output_adv, output_s, bpp_ori, bpp, mse, vi
+
+    def attack(self, items):
+        """items: list of (name, tensor|None, H, W) of one image size; returns per-image results."""
+        ims, im_s, im_adv, output_adv, output_s, bpp_ori, bpp, mse, vi = self.run(items)
         out = []
         for b, (name, _, _, _) in enumerate(items):
             v = dict(vi[b])
@@ -198,18 +204,20 @@ def _dist_setup(args):
     return rank, world, group
 
 
-def batch_attack(args):
-    """attack_rd.batch_attack (attack_rd.py:646-699).  Under torchrun the sorted image list is split into
-    contiguous per-rank shards (dist.shard_range); every rank attacks its shard with no collective, the
-    per-image result tuples are gathered to rank 0 once at the end, and rank 0 prints the reference's
-    per-image lines (:670) in reference order and the AVG line (:688)."""
+def collect_results(args, attacker_cls=None):
+    """Attack every image of args.source with ``attacker_cls`` (default: this module's attacker): one
+    (name, bpp_ori, bpp, vi_results, seconds) per image in reference order.  Under torchrun the sorted image
+    list is split into contiguous per-rank shards (dist.shard_range); every rank attacks its shard with no
+    collective, the per-image result tuples are gathered to rank 0 once at the end, and every other rank gets
+    None.  Shared by the CLIs that print their own lines from these tuples (attack_patch)."""
     from . import dist as D
+    attacker_cls = attacker_cls or attacker
     rank, world, group = _dist_setup(args)
     if rank == 0:
-        myattacker = attacker(args)
+        myattacker = attacker_cls(args)
     else:   # settings banners once, from rank 0 (the output matches a one-process run line for line)
         with contextlib.redirect_stdout(io.StringIO()):
-            myattacker = attacker(args)
+            myattacker = attacker_cls(args)
     items = _sources(args.source)
     shard = D.shard_range(len(items), rank, world)
     results = _attack_items(myattacker, [items[i] for i in shard], args)
@@ -223,6 +231,15 @@ def batch_attack(args):
             return None
         results = [r for part in gathered for r in part]
         tdist.barrier(group=group)
+    return results
+
+
+def batch_attack(args):
+    """attack_rd.batch_attack (attack_rd.py:646-699): collect_results, then rank 0 prints the reference's
+    per-image lines (:670) in reference order and the AVG line (:688)."""
+    results = collect_results(args)
+    if results is None:
+        return None
     bpp_ori_, bpp_, vi_, vi_anchor_, vi_msim_, t_ = 0.0, 0.0, 0.0, 0.0, 0.0, 0.0
     n_done = 0
     for name, bpp_ori, bpp, vi_results, per_t in results:

@@ -389,6 +389,22 @@ int ica_latent_clamp_bwd(float* g4, const float* y4, const float* cmax, const fl
 int ica_latent_detect(const float* imax, const float* imin, const float* cmax, const float* cmin, float* score, int B,
                       int C, hipStream_t stream);
 
+/* ---- patch-wise VI localisation (ica_patch.hip) ----------------------------
+ * psnr_partial (attack_patch.py:119-146) on four planar NCHW fp32 tensors [B][3][H][W], per image.  With
+ * nh = (H - win) / stride + 1 and nw likewise: mse_in / mse_out [B][nh][nw] are the means over the 3 * win^2 window
+ * elements of (im_s - im_adv)^2 and (out_s - out_adv)^2; vi = mse_out / mse_in, 0 on the `border` rows and columns
+ * at each edge and where mse_in == 0; val[B] / pos[B][2] (row, col of the map; pixel origin = pos * stride) are
+ * the largest vi and its first row-major position.  Accepted: stride in {1, 2, 4}, win % stride == 0, win <= 128,
+ * H, W >= win, W % 4 == 0, border >= 0, W / stride <= 8192; anything else returns -5 and launches nothing.
+ * ws: ica_patch_vi_ws_size floats; key_ws: 8 * B bytes (both scratch). */
+size_t ica_patch_vi_ws_size(int B, int H, int W, int win, int stride);
+int ica_patch_vi(const float* im_adv, const float* out_adv, const float* im_s, const float* out_s, int B, int H, int W,
+                 int win, int stride, int border, float* ws, void* key_ws, float* mse_in, float* mse_out, float* vi,
+                 float* val, int* pos, hipStream_t stream);
+/* patches[B][4][3][win][win] = (im_adv, out_adv, im_s, out_s) cut at pos * stride, pos [B][2] read on the device. */
+int ica_patch_gather(const float* im_adv, const float* out_adv, const float* im_s, const float* out_s, const int* pos,
+                     float* patches, int B, int H, int W, int win, int stride, hipStream_t stream);
+
 /* ---- MS-SSIM (ica_msssim.hip) ---------------------------------------------- */
 /* mode 0 = pytorch_msssim (valid, per-channel, relu), mode 1 = utils/torch_msssim (same-pad, global). */
 int ica_msssim_blocks(int H, int W, int ws, int mode);
