@@ -405,6 +405,36 @@ int ica_patch_vi(const float* im_adv, const float* out_adv, const float* im_s, c
 int ica_patch_gather(const float* im_adv, const float* out_adv, const float* im_s, const float* out_s, const int* pos,
                      float* patches, int B, int H, int W, int win, int stride, hipStream_t stream);
 
+/* ---- image-space degradations (ica_degrade.hip) -----------------------------
+ * random_noise.py's blur, sigma scan and additive noise on planar NCHW fp32 tensors [B][3][H][W] (16-byte aligned).
+ * Status: 0, -5 for an unsupported problem or a missing / misaligned pointer, -7 for an output that overlaps the
+ * input of the blur; nothing is launched then.  Every workspace is scratch, in floats, sized by its *_ws_size query
+ * (0 for an unsupported problem).  All reductions are fixed-order: an image's numbers do not depend on the batch.
+ *
+ * ica_gauss_blur: torchvision gaussian_blur.  Reflect padding without edge repeat (kx / 2 columns, ky / 2 rows),
+ * then out = sum_{i, j} (wy[b][i] * wx[b][j]) * x_padded[y + i][x + j] per channel, the weight one rounded fp32
+ * product, the sum one fmaf chain in row-major tap order.  wx [B][kx], wy [B][ky] on the device; kx, ky odd in
+ * 1 .. 9, W % 4 == 0, H > ky / 2, W > kx / 2.  clamp != 0 clamps out to [0, 1].  ref (optional, with mse and ws):
+ * mse[b] = mean((out - ref)^2). */
+size_t ica_gauss_blur_ws_size(int B, int H, int W);
+int ica_gauss_blur(const float* x, const float* wx, const float* wy, int B, int H, int W, int kx, int ky, int clamp,
+                   const float* ref, float* out, float* mse, float* ws, hipStream_t stream);
+/* ica_blur_sweep: S <= ica_blur_sweep_chunk() candidate kernels wx [S][kx], wy [S][ky] shared by all images; for
+ * every image with done[b] == 0: mse[b * ld + s0 + s] = mean((clamp(blur_s(x), 0, 1) - x)^2) (the arithmetic of
+ * ica_gauss_blur; no image is written), then idx[b] = s0 + (first s with mse <= budget) and done[b] = 1 if there is
+ * one.  remaining[0] = images still without an answer.  Images with done[b] != 0 cost nothing and keep their mse
+ * row.  The caller zeroes done and sets idx to -1 before the first chunk. */
+int ica_blur_sweep_chunk(void);
+size_t ica_blur_sweep_ws_size(int B, int H, int W);
+int ica_blur_sweep(const float* x, const float* wx, const float* wy, int S, int B, int H, int W, int kx, int ky,
+                   float budget, int s0, float* mse, long ld, int* idx, int* done, int* remaining, float* ws,
+                   hipStream_t stream);
+/* ica_noise_apply (random_noise.py:80): out = clamp(im + noise, 0, 1) (out a third buffer), noise_power[b] =
+ * mean(noise^2), mse_in[b] = mean((out - im)^2).  W % 4 == 0. */
+size_t ica_noise_apply_ws_size(int B, int H, int W);
+int ica_noise_apply(const float* im, const float* noise, float* out, int B, int H, int W, float* noise_power,
+                    float* mse_in, float* ws, hipStream_t stream);
+
 /* ---- MS-SSIM (ica_msssim.hip) ---------------------------------------------- */
 /* mode 0 = pytorch_msssim (valid, per-channel, relu), mode 1 = utils/torch_msssim (same-pad, global). */
 int ica_msssim_blocks(int H, int W, int ws, int mode);
