@@ -435,6 +435,25 @@ size_t ica_noise_apply_ws_size(int B, int H, int W);
 int ica_noise_apply(const float* im, const float* noise, float* out, int B, int H, int W, float* noise_power,
                     float* mse_in, float* ws, hipStream_t stream);
 
+/* ---- perturbation transfer (ica_transfer.hip) -------------------------------
+ * The pair loop of transfer_noise.py for N noises x M target images of one size, pair (i, j) at index i * M + j.
+ * Status as above: -5 for an unsupported problem (N, M < 1, M > 65535, N > 4 * 65535, N * M >= 2^21, H * W >= 2^29) or a
+ * missing / misaligned pointer, -7 for an im_in that overlaps im or noise; nothing is launched then.  ws: scratch of
+ * the *_ws_size floats (0 for an unsupported problem).  Reductions are fixed-order and a pair's blocks depend on
+ * (H, W) only: a pair's numbers are the same bits alone (N = M = 1) and in any block of pairs.
+ *
+ * ica_transfer_apply (transfer_noise.py:88-89): im [M][3][H][W], noise [N][3][H][W] planar NCHW fp32, W % 4 == 0;
+ * im_in[i * M + j] = clamp(im[j] + noise[i], 0, 1) ([N * M][3][H][W]), mse_in[i][j] = mean((im_in - im[j])^2).
+ * ica_transfer_score (transfer_noise.py:96, :133): x_hat4 [N * M][H][W][4], x_s4 [M][H][W][4] nChw4c fp32 of 3
+ * channels; mse_out[i][j] = mean over the 3 real channels of (c(x_hat4[i * M + j]) - c(x_s4[j]))^2 with c = clamp to
+ * [0, 1] if `clamp`, else the identity.  The padding lane is loaded and never used. */
+size_t ica_transfer_apply_ws_size(int N, int M, int H, int W);
+int ica_transfer_apply(const float* im, const float* noise, float* im_in, int N, int M, int H, int W, float* mse_in,
+                       float* ws, hipStream_t stream);
+size_t ica_transfer_score_ws_size(int N, int M, int H, int W);
+int ica_transfer_score(const float* x_hat4, const float* x_s4, int N, int M, int H, int W, int clamp, float* mse_out,
+                       float* ws, hipStream_t stream);
+
 /* ---- MS-SSIM (ica_msssim.hip) ---------------------------------------------- */
 /* mode 0 = pytorch_msssim (valid, per-channel, relu), mode 1 = utils/torch_msssim (same-pad, global). */
 int ica_msssim_blocks(int H, int W, int ws, int mode);
