@@ -104,6 +104,12 @@ _SIGS = {
     "ica_transfer_apply": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "ica_transfer_score_ws_size": [_i, _i, _i, _i],
     "ica_transfer_score": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
+    # iterated re-compression: the step between two generations (ica_recompress.hip)
+    "ica_requant8_ws_size": [_i, _i, _i],
+    "ica_requant8": [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "ica_quant8_pack": [_p, _i, _i, _i, _p, _p, _p],
+    "ica_floor_bits_ws_size": [_i, _i, _i, _i],
+    "ica_floor_bits": [_p, _i, _i, _i, _i, _f, _p, _p, _p],
     "ica_gc_symbols": [_p, _p, _p, _p, _i, _f, _p, _p, _i, _i, _i, _i, _p],
     "ica_eb_symbols": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ica_dequantize": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
@@ -149,7 +155,8 @@ _RESTYPES = {"ica_pack_conv_weight_size": _sz, "ica_pack_conv_weight_bf16_size":
              "ica_pack_conv_weight_x6_size": _sz, "ica_pack_gdn_x6_size": _sz, "ica_pack_up3k3_x6_size": _sz, "ica_pack_up3_size": _sz, "ica_wgrad_ws_size": _sz,
              "ica_rans_encode": _l, "ica_ar_lds_bytes": _sz, "ica_patch_vi_ws_size": _sz,
              "ica_gauss_blur_ws_size": _sz, "ica_blur_sweep_ws_size": _sz, "ica_noise_apply_ws_size": _sz,
-             "ica_transfer_apply_ws_size": _sz, "ica_transfer_score_ws_size": _sz}
+             "ica_transfer_apply_ws_size": _sz, "ica_transfer_score_ws_size": _sz,
+             "ica_requant8_ws_size": _sz, "ica_floor_bits_ws_size": _sz}
 
 
 

@@ -454,6 +454,35 @@ size_t ica_transfer_score_ws_size(int N, int M, int H, int W);
 int ica_transfer_score(const float* x_hat4, const float* x_s4, int N, int M, int H, int W, int clamp, float* mse_out,
                        float* ws, hipStream_t stream);
 
+/* ---- iterated re-compression (ica_recompress.hip) ---------------------------
+ * The step between two generations of recompression.py (coder.py:21-48), on the device and for a whole batch.
+ * Images are B x 3 x H x W; codes are one uint32 per pixel, r | g << 8 | b << 16, [B][H][W] (the top byte is written
+ * 0 and ignored on input).  Status: 0, or -5 and nothing launched for B < 1, B > 65535, H < 1, W % 4 != 0,
+ * H * W > 2^29 - 1, a missing pointer or an nChw4c pointer that is not 16-byte aligned.  Workspaces are scratch, in
+ * floats, sized by the *_ws_size query (0 for an unsupported problem).  Reductions are fixed-order and an image's
+ * blocks depend on H * W only: an image's numbers are the same bits alone and in a batch.
+ *
+ * ica_requant8: x_hat4 [B][1][H][W][4] nChw4c fp32 (unclamped, lane 3 never used), orig [B][3][H][W] planar.
+ * With c = clamp(x_hat, 0, 1) and k = (uint)rint(c * 255) (fp32 product, half-to-even) per channel:
+ *   q = the packed k;  next4 lanes 0..2 = (float)k / 255.0f (correctly rounded), lane 3 = 0;
+ *   out (planar [B][3][H][W], NULL to skip) = c;
+ *   sse_orig[b] = sum (c - orig)^2;  sse_gen[b] = sum ((k - k_prev) / 255)^2;
+ *   changed[b] = the number of the 3 H W code values that differ from prev_q (exact);
+ *   moving[0] (NULL to skip) = the number of images with changed != 0.
+ * A NaN in x_hat clamps to 0: code 0, out 0.  next4 may be x_hat4 and q may be prev_q (a pixel is read before it is
+ * written, by the same thread).
+ * ica_quant8_pack: planar im -> q and next4 by the same clamp, rounding and division (generation 0).
+ * ica_floor_bits: bits[b] = sum over c < C, pixels of log(max(lik, floor)) of lik4 [B][ceil(C / 4)][H][W][4] (natural
+ * log; floor > 0; a NaN counts as the floor); any W, C * H * W limited to 2^30 quads. */
+size_t ica_requant8_ws_size(int B, int H, int W);
+int ica_requant8(const float* x_hat4, const float* orig, const uint32_t* prev_q, int B, int H, int W, float* next4,
+                 uint32_t* q, float* out, float* sse_orig, float* sse_gen, long long* changed, int* moving, float* ws,
+                 hipStream_t stream);
+int ica_quant8_pack(const float* im, int B, int H, int W, float* next4, uint32_t* q, hipStream_t stream);
+size_t ica_floor_bits_ws_size(int B, int C, int H, int W);
+int ica_floor_bits(const float* lik4, int B, int C, int H, int W, float floor, float* bits, float* ws,
+                   hipStream_t stream);
+
 /* ---- MS-SSIM (ica_msssim.hip) ---------------------------------------------- */
 /* mode 0 = pytorch_msssim (valid, per-channel, relu), mode 1 = utils/torch_msssim (same-pad, global). */
 int ica_msssim_blocks(int H, int W, int ws, int mode);
