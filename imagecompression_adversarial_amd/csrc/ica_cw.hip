@@ -14,29 +14,27 @@
 //                        levels (levels completed), active, reset
 // loss_i and mse_o are fp32 and are compared against the double thresholds rounded to fp32, as torch compares
 // a fp32 tensor with a Python scalar.
-#include "ica_common.h"
+#include "ica_reduce.h"
 
 enum { CW_CL = 0, CW_CR = 1, CW_C = 2, CW_LEVEL = 3, CW_MIN = 4, CW_MAX = 5 };
 enum { CW_T = 0, CW_ROUND = 1, CW_LEVELS = 2, CW_ACTIVE = 3, CW_RESET = 4 };
 
-// mse_o[b] = invN * sum_k part[b][k] in reduce_rows_kernel's order (strided slices, wave tree, then
-// (w0 + w1) + (w2 + w3)), then the gate on the loss weight and the image's Adam step count.  One block per image.
+// mse_o[b] = invN * sum_k part[b][k] in reduce_rows_kernel's order (strided slices, then the paired block_sum of
+// ica_reduce.h), then the gate on the loss weight and the image's Adam step count.  One block per image.
 __global__ void cw_gate_kernel(const float* __restrict__ part, int nblk, float invN, const double* __restrict__ sd,
                                int* __restrict__ si, float* __restrict__ mse_o, float* __restrict__ c_eff, int B) {
   __shared__ float sh[4];
   const int b = blockIdx.x;
   float v = 0.f;
   for (int k = threadIdx.x; k < nblk; k += 256) v += part[(long)b * nblk + k];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
+  const float sum = block_sum_paired(v, sh);
   if (threadIdx.x != 0) return;
   const int active = si[CW_ACTIVE * B + b];
   if (!active) {   // a finished image keeps its last mse_o; its Adam launch is skipped
     c_eff[b] = 0.f;
     return;
   }
-  const float mse = ((sh[0] + sh[1]) + (sh[2] + sh[3])) * invN;
+  const float mse = sum * invN;
   mse_o[b] = mse;
   c_eff[b] = mse > (float)(sd[CW_LEVEL * B + b] * 1.1) ? 0.f : (float)sd[CW_C * B + b];
   si[CW_T * B + b] += 1;
@@ -165,7 +163,7 @@ __global__ void cw_round_kernel(const float* __restrict__ loss_i, const float* _
     si[CW_RESET * B + b] = 1;
     ++cnt;
   }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  cnt = wave_sum(cnt);
   if (threadIdx.x == 0) *n_active = cnt;
 }
 

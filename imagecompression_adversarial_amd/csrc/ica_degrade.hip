@@ -14,10 +14,8 @@
 // the image, reflected scalar loads at its edges); each thread then holds the window of its 4 x 2 output pixels in
 // registers, so the sweep scores every candidate of the chunk without touching LDS or HBM again.
 //
-// Reductions: a thread's squared errors in a fixed chain, the block's 256 threads in a fixed tree, one partial per
-// block, and the partials of an image summed by one wave in index order.  The grid of an image depends on (H, W)
-// only and no float atomic is used, so an image's numbers are the same bits alone and in a batch, run to run.
-#include "ica_common.h"
+// Reductions: ica_reduce.h (sequential block order; one partial per tile, NOISE_MAX_BLOCKS caps noise_apply's).
+#include "ica_reduce.h"
 
 namespace {
 
@@ -101,18 +99,6 @@ ICA_DEV void correlate(const float (&v)[DG_WIN][12], const float* __restrict__ w
       }
     }
   }
-}
-
-ICA_DEV float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }   // keeps a NaN, as torch.clamp
-
-// sum over the block in a fixed order (wave butterfly, then the four waves in index order); red: 4 floats of LDS
-ICA_DEV float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float s = fadd_rn(fadd_rn(fadd_rn(red[0], red[1]), red[2]), red[3]);
-  __syncthreads();
-  return s;
 }
 
 template <int KX>
@@ -206,20 +192,6 @@ __global__ __launch_bounds__(DG_THREADS) void blur_sweep_kernel(const float* __r
   }
 }
 
-// out[(row / rpi) * ld + off + row % rpi] = (sum of the row's n partials) / count: lane l adds the partials l, l + 64,
-// ... in that order, then the butterfly.  done (optional): rows of finished images are left alone.
-__global__ __launch_bounds__(64) void degrade_finish_kernel(const float* __restrict__ part, int n, float count,
-                                                            float* __restrict__ out, int rpi, long ld, long off,
-                                                            const int* __restrict__ done) {
-  const int row = blockIdx.x, img = row / rpi;
-  if (done && done[img]) return;
-  const float* p = part + (size_t)row * n;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 64) s = fadd_rn(s, p[i]);
-  s = wave_sum(s);
-  if (threadIdx.x == 0) out[(size_t)img * ld + off + (row - img * rpi)] = fdiv_rn(s, count);
-}
-
 // one block: per unfinished image the first candidate of this chunk with mse <= budget; remaining[0] = images still
 // without an answer
 __global__ __launch_bounds__(DG_THREADS) void sweep_select_kernel(const float* __restrict__ mse, long ld, int s0, int S,
@@ -275,8 +247,6 @@ __global__ __launch_bounds__(DG_THREADS) void noise_apply_kernel(const float* __
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // 0 if (B, H, W, kx, ky) is a supported blur problem
 int blur_check(int B, int H, int W, int kx, int ky) {
   if (B < 1 || B > 21845) return -5;   // 3 B planes on grid.z
@@ -286,10 +256,7 @@ int blur_check(int B, int H, int W, int kx, int ky) {
   return 0;
 }
 int tiles_of(int H, int W) { return ((W + DG_TW - 1) / DG_TW) * ((H + DG_TH - 1) / DG_TH); }
-int noise_blocks(long quads) {
-  const long g = (quads + DG_THREADS - 1) / DG_THREADS;
-  return (int)(g > NOISE_MAX_BLOCKS ? NOISE_MAX_BLOCKS : g);
-}
+int noise_blocks(long quads) { return capped_blocks(quads, DG_THREADS, NOISE_MAX_BLOCKS); }
 
 #define DG_DISPATCH_KX(kern, kx, grid, st, ...)                                                  \
   do {                                                                                           \
@@ -320,16 +287,13 @@ int ica_gauss_blur(const float* x, const float* wx, const float* wy, int B, int 
   if (!x || !wx || !wy || !out || (ref && (!mse || !ws)) || (!ref && mse)) return -5;
   if (!aligned16(x) || !aligned16(out) || !aligned16(ref)) return -5;
   const size_t bytes = (size_t)B * 3 * H * W * sizeof(float);
-  const char* xb = reinterpret_cast<const char*>(x);
-  const char* ob = reinterpret_cast<const char*>(out);
-  if (xb < ob + bytes && ob < xb + bytes) return -7;   // a tile's halo is read after its neighbour was written
+  if (overlaps(x, bytes, out, bytes)) return -7;   // a tile's halo is read after its neighbour was written
   const dim3 grid((W + DG_TW - 1) / DG_TW, (H + DG_TH - 1) / DG_TH, 3 * B);
   float* part = ref ? ws : nullptr;
   DG_DISPATCH_KX(gauss_blur_kernel, kx, grid, st, x, wx, wy, ky, H, W, clamp, ref, out, part);
   ICA_CHECK_LAUNCH();
   if (ref) {
-    ICA_LAUNCH(degrade_finish_kernel, dim3(B), dim3(64), 0, st, (const float*)ws, 3 * tiles_of(H, W),
-               (float)((long)3 * H * W), mse, 1, 1L, 0L, (const int*)nullptr);
+    finish_rows(st, ws, B, 3 * tiles_of(H, W), (float)((long)3 * H * W), mse);
     ICA_CHECK_LAUNCH();
   }
   return 0;
@@ -350,8 +314,7 @@ int ica_blur_sweep(const float* x, const float* wx, const float* wy, int S, int 
   const dim3 grid((W + DG_TW - 1) / DG_TW, (H + DG_TH - 1) / DG_TH, 3 * B);
   DG_DISPATCH_KX(blur_sweep_kernel, kx, grid, st, x, wx, wy, S, ky, H, W, (const int*)done, ws);
   ICA_CHECK_LAUNCH();
-  ICA_LAUNCH(degrade_finish_kernel, dim3(B * S), dim3(64), 0, st, (const float*)ws, 3 * tiles_of(H, W),
-             (float)((long)3 * H * W), mse, S, ld, (long)s0, (const int*)done);
+  finish_rows(st, ws, B * S, 3 * tiles_of(H, W), (float)((long)3 * H * W), mse, S, ld, s0, done);
   ICA_CHECK_LAUNCH();
   ICA_LAUNCH(sweep_select_kernel, dim3(1), dim3(DG_THREADS), 0, st, (const float*)mse, ld, s0, S, budget, B, idx, done,
              remaining);
@@ -376,11 +339,9 @@ int ica_noise_apply(const float* im, const float* noise, float* out, int B, int 
   ICA_LAUNCH(noise_apply_kernel, dim3(nb, B), dim3(DG_THREADS), 0, st, im, noise, out, quads, part_noise, part_in);
   ICA_CHECK_LAUNCH();
   const float count = (float)((long)3 * H * W);
-  ICA_LAUNCH(degrade_finish_kernel, dim3(B), dim3(64), 0, st, (const float*)part_noise, nb, count, noise_power, 1, 1L,
-             0L, (const int*)nullptr);
+  finish_rows(st, part_noise, B, nb, count, noise_power);
   ICA_CHECK_LAUNCH();
-  ICA_LAUNCH(degrade_finish_kernel, dim3(B), dim3(64), 0, st, (const float*)part_in, nb, count, mse_in, 1, 1L, 0L,
-             (const int*)nullptr);
+  finish_rows(st, part_in, B, nb, count, mse_in);
   ICA_CHECK_LAUNCH();
   return 0;
 }

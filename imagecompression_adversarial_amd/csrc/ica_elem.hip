@@ -10,7 +10,7 @@
 //   I-FGSM / MI-FGSM update           attack_ifgsm.py:348-362,393-419
 //   EntropyBottleneck / GaussianConditional likelihoods, bpp
 //                                     anchors/model.py:86-108, attack_rd.py:419 (CompressAI semantics)
-#include "ica_common.h"
+#include "ica_reduce.h"
 
 // ---------------------------------------------------------------------------
 // Layout conversion  NCHW <-> nChw4c (padded channels are written as zero)
@@ -54,25 +54,14 @@ __global__ void nc4_to_nchw_kernel(const float* __restrict__ src, float* __restr
 
 // ---------------------------------------------------------------------------
 // Deterministic per-image reduction: partial[b][k] for k < nblk -> out[b]
-// (fixed order: each block reduces a strided slice, then a single-wave tree).
+// (fixed order: each block reduces a strided slice, then the paired block_sum of ica_reduce.h).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float r = 0.f;
-  if (threadIdx.x == 0) r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  return r;
-}
-
 __global__ void reduce_rows_kernel(const float* __restrict__ part, float* __restrict__ out, int nblk, float scale) {
   __shared__ float sh[4];
   const int b = blockIdx.x;
   float v = 0.f;
   for (int k = threadIdx.x; k < nblk; k += 256) v += part[(long)b * nblk + k];
-  const float r = block_sum_256(v, sh);
+  const float r = block_sum_paired(v, sh);
   if (threadIdx.x == 0) out[b] = r * scale;
 }
 
@@ -108,7 +97,7 @@ __global__ void attack_prologue_kernel(const float* __restrict__ noise, const fl
     }
     st4(o4 + pix * 4, v);
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 
@@ -145,7 +134,7 @@ __global__ void attack_loss_kernel(const float* __restrict__ xhat4, const float*
     }
     st4(g4 + pix * 4, gv);
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 
@@ -177,7 +166,7 @@ __global__ void roi_prologue_kernel(const float* __restrict__ noise, const float
     }
     st4(o4 + pix * 4, v);
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 
@@ -214,7 +203,7 @@ __global__ void roi_loss_kernel(const float* __restrict__ xhat4, const float* __
     }
     st4(g4 + pix * 4, gv);
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 
@@ -390,7 +379,7 @@ __global__ void l1_partial_kernel(const float* __restrict__ g4, float* __restric
     const f32x4 v = ld4(g4 + ((long)b * HW + pix) * 4);
     acc += (fabsf(v[0]) + fabsf(v[1])) + fabsf(v[2]);
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 
@@ -433,7 +422,7 @@ __global__ void gc_kernel(const float* __restrict__ y, const float* __restrict__
     if (lik) lik[i] = l;
     acc += logf(l);
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 
@@ -497,7 +486,7 @@ __global__ void eb_kernel(const float* __restrict__ z, const float* __restrict__
     if (lik) lik[i] = l;
     acc += logf(l);
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 
@@ -572,7 +561,7 @@ __global__ void sqdiff_partial_kernel(const float* __restrict__ a, const float* 
     const float d = fsub_rn(x, b_[(long)b * len + k]);
     acc = fadd_rn(acc, fmul_rn(d, d));
   }
-  const float r = block_sum_256(acc, sh);
+  const float r = block_sum_paired(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = r;
 }
 

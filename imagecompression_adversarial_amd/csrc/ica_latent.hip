@@ -13,7 +13,7 @@
 // reductions carry a NaN flag next to the running extreme.
 #include <math.h>
 
-#include "ica_common.h"
+#include "ica_reduce.h"
 
 #define LAT_THREADS 256
 #define LAT_WAVES (LAT_THREADS / 64)
@@ -31,11 +31,6 @@ ICA_DEV float wave_min(float v) {
 ICA_DEV int wave_or(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
-ICA_DEV int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_clamp_kernel(const float* 
     st4(dst + q * 4, o);
   }
   if (nclamped) {
-    cnt = wave_isum(cnt);
+    cnt = wave_sum(cnt);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(nclamped + b, cnt);
   }
 }
@@ -195,10 +190,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_detect_kernel(const float*
   }
 }
 
-static inline int lat_blocks_per_image(long quads) {
-  long g = (quads + LAT_THREADS - 1) / LAT_THREADS;
-  return (int)(g > 1024 ? 1024 : (g < 1 ? 1 : g));
-}
+static inline int lat_blocks_per_image(long quads) { return max(1, capped_blocks(quads, LAT_THREADS, 1024)); }
 static inline int lat_check(int B, int C, int H, int W) {
   if (C <= 0 || C % 4 != 0) return -2;
   if (B <= 0 || H <= 0 || W <= 0 || B > 65535 || (long)H * W > 0x7fffffffL / 4) return -5;

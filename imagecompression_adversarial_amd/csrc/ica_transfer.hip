@@ -5,32 +5,19 @@
 //   transfer_score_kernel   transfer_noise.py:96, :133: mean over the 3 real channels of (clamp(x_hat4[i * M + j]) -
 //                           clamp(x_s4[j]))^2, read from the nChw4c tensors the decoder leaves; no NCHW copy of the
 //                           N * M reconstructions and no expanded reference tensor is written
-//   pair_finish_kernel      one wave per pair sums the pair's block partials in index order
 //
 // Both kernels stream: grid (blocks, M, ceil(N / TN)).  A thread loads a quad of target j once and reuses it for the
 // TN noises (reconstructions) of its tile, so a pair costs one 16-byte load and, for apply, one 16-byte store per
 // quad, plus 1 / TN of the target's.  Arithmetic as noise_apply_kernel (ica_degrade.hip): fadd_rn, clamp, fsub_rn,
-// one fmaf chain per thread; the block's 256 threads in a fixed tree; no float atomic.  The blocks of a pair depend
-// on (H, W) only, so a pair's numbers are the same bits whatever N, M and the tile remainder are, run to run.
-#include "ica_common.h"
+// one fmaf chain per thread.  Reductions: ica_reduce.h (sequential block order, one row of partials per pair), so a
+// pair's numbers do not depend on N, M or the tile remainder.
+#include "ica_reduce.h"
 
 namespace {
 
 constexpr int TR_THREADS = 256;
 constexpr int TR_TN = 4;                  // noises per thread tile (grid.z = ceil(N / TR_TN))
 constexpr int TR_MAX_BLOCKS = 1024;       // blocks per pair, as ica_noise_apply
-
-ICA_DEV float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }   // keeps a NaN, as torch.clamp
-
-// sum over the block in a fixed order (wave butterfly, then the four waves in index order); red: 4 floats of LDS
-ICA_DEV float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float s = fadd_rn(fadd_rn(fadd_rn(red[0], red[1]), red[2]), red[3]);
-  __syncthreads();
-  return s;
-}
 
 // quads: 3 H W / 4 floats-of-four per image.  part[(i * M + j) * gridDim.x + blockIdx.x]
 __global__ __launch_bounds__(TR_THREADS) void transfer_apply_kernel(const float* __restrict__ im,
@@ -115,25 +102,6 @@ __global__ __launch_bounds__(TR_THREADS) void transfer_score_kernel(const float*
   }
 }
 
-// out[pair] = (sum of the pair's n partials) / count: lane l adds the partials l, l + 64, ... in that order, then the
-// butterfly (what degrade_finish_kernel does for an image)
-__global__ __launch_bounds__(64) void pair_finish_kernel(const float* __restrict__ part, int n, float count,
-                                                         float* __restrict__ out) {
-  const float* p = part + (size_t)blockIdx.x * n;
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 64) s = fadd_rn(s, p[i]);
-  s = wave_sum(s);
-  if (threadIdx.x == 0) out[blockIdx.x] = fdiv_rn(s, count);
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
-  const char* pa = static_cast<const char*>(a);
-  const char* pb = static_cast<const char*>(b);
-  return pa < pb + bbytes && pb < pa + abytes;
-}
-
 // 0 if the grid holds N x M pairs of H x W images (grid.y = M, grid.z = ceil(N / TN), finish grid.x = N M)
 int pairs_check(int N, int M, int H, int W) {
   if (N < 1 || M < 1 || M > 65535 || (N + TR_TN - 1) / TR_TN > 65535) return -5;
@@ -142,10 +110,7 @@ int pairs_check(int N, int M, int H, int W) {
   return 0;
 }
 
-int stream_blocks(long units) {
-  const long g = (units + TR_THREADS - 1) / TR_THREADS;
-  return (int)(g > TR_MAX_BLOCKS ? TR_MAX_BLOCKS : g);
-}
+int stream_blocks(long units) { return capped_blocks(units, TR_THREADS, TR_MAX_BLOCKS); }
 
 }  // namespace
 
@@ -170,8 +135,7 @@ int ica_transfer_apply(const float* im, const float* noise, float* im_in, int N,
   ICA_LAUNCH(transfer_apply_kernel, dim3(nb, M, (N + TR_TN - 1) / TR_TN), dim3(TR_THREADS), 0, st, im, noise, im_in,
              quads, N, ws);
   ICA_CHECK_LAUNCH();
-  ICA_LAUNCH(pair_finish_kernel, dim3(N * M), dim3(64), 0, st, (const float*)ws, nb, (float)((long)3 * H * W),
-             mse_in);
+  finish_rows(st, ws, N * M, nb, (float)((long)3 * H * W), mse_in);
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -194,8 +158,7 @@ int ica_transfer_score(const float* x_hat4, const float* x_s4, int N, int M, int
   else
     ICA_LAUNCH(transfer_score_kernel<false>, grid, dim3(TR_THREADS), 0, st, x_hat4, x_s4, pixels, N, ws);
   ICA_CHECK_LAUNCH();
-  ICA_LAUNCH(pair_finish_kernel, dim3(N * M), dim3(64), 0, st, (const float*)ws, nb, (float)((long)3 * H * W),
-             mse_out);
+  finish_rows(st, ws, N * M, nb, (float)((long)3 * H * W), mse_out);
   ICA_CHECK_LAUNCH();
   return 0;
 }

@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import torch
 
 from . import hip_ops as K
-from ._lib import lib, ptr, stream
+from ._lib import call, lib, ptr, stream
 
 KMAX = 9
 BLUR_KSIZE, BLUR_SIGMA = (5, 9), 0.5          # random_noise.py:31
@@ -49,9 +49,8 @@ def sigma_schedule(start=SIGMA_START, step=SIGMA_STEP):
 def validate(H, W, kernel_size=BLUR_KSIZE, sigma=BLUR_SIGMA, noise=None, factor=SWEEP_FACTOR, start=SIGMA_START,
              step=SIGMA_STEP):
     """ValueError unless the kernels take this problem (include/ica_hip.h, ica_gauss_blur / ica_blur_sweep)."""
-    for name, v in (("H", H), ("W", W)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise ValueError(f"{name} must be a positive int, got {v!r}")
+    K.positive_int("H", H)
+    K.positive_int("W", W)
     if (not isinstance(kernel_size, (tuple, list)) or len(kernel_size) != 2
             or any(not isinstance(k, int) or isinstance(k, bool) for k in kernel_size)):
         raise ValueError(f"kernel_size must be two ints (kx, ky), got {kernel_size!r}")
@@ -78,19 +77,6 @@ def validate(H, W, kernel_size=BLUR_KSIZE, sigma=BLUR_SIGMA, noise=None, factor=
             raise ValueError(f"the schedule start={start!r}, step={step!r} has more than 1e6 candidates")
 
 
-def _check_image(x, name="x"):
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError(f"{name} {tuple(x.shape)} is not a [B, 3, H, W] batch")
-    K._dev_check(x, name)
-    return x.shape[0], x.shape[2], x.shape[3]
-
-
-def _call(name, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with status {rc}")
-
-
 def _ws(name, B, H, W, dev):
     return torch.empty(getattr(lib(), name)(B, H, W), dtype=torch.float32, device=dev)
 
@@ -98,7 +84,7 @@ def _ws(name, B, H, W, dev):
 def gaussian_blur(x, kernel_size=BLUR_KSIZE, sigma=BLUR_SIGMA, clamp=False, ref=None):
     """torchvision's gaussian_blur of x.  ``kernel_size`` is (kx, ky) as in torchvision; ``sigma`` a float or one per
     image.  With ``ref`` returns (blurred, mean((blurred - ref)^2) [B]), else the blurred batch."""
-    B, H, W = _check_image(x)
+    B, H, W = K.check_image(x, "x")
     sig = [float(s) for s in sigma] if isinstance(sigma, (tuple, list)) else [float(sigma)] * B
     validate(H, W, tuple(kernel_size), sig)
     if len(sig) != B:
@@ -116,7 +102,7 @@ def gaussian_blur(x, kernel_size=BLUR_KSIZE, sigma=BLUR_SIGMA, clamp=False, ref=
     if ref is not None:
         mse = torch.empty(B, dtype=torch.float32, device=x.device)
         ws = _ws("ica_gauss_blur_ws_size", B, H, W, x.device)
-    _call("ica_gauss_blur", ptr(x), ptr(wx), ptr(wy), B, H, W, kx, ky, int(bool(clamp)), ptr(ref), ptr(out), ptr(mse),
+    call("ica_gauss_blur", ptr(x), ptr(wx), ptr(wy), B, H, W, kx, ky, int(bool(clamp)), ptr(ref), ptr(out), ptr(mse),
           ptr(ws), stream())
     return out if ref is None else (out, mse)
 
@@ -124,7 +110,7 @@ def gaussian_blur(x, kernel_size=BLUR_KSIZE, sigma=BLUR_SIGMA, clamp=False, ref=
 def blur_sweep(x, sigmas, noise, ksize=SWEEP_KSIZE, factor=SWEEP_FACTOR):
     """Scores the candidates ``sigmas`` in order, a chunk per launch, until every image has its first fit:
     (index [B] int32 on the device, -1 where none fits; mse [B, len(sigmas)], NaN where a candidate was not needed)."""
-    B, H, W = _check_image(x)
+    B, H, W = K.check_image(x, "x")
     validate(H, W, tuple(ksize), list(sigmas), noise, factor)
     kx, ky = ksize
     dev = x.device
@@ -139,7 +125,7 @@ def blur_sweep(x, sigmas, noise, ksize=SWEEP_KSIZE, factor=SWEEP_FACTOR):
     chunk = lib().ica_blur_sweep_chunk()
     for s0 in range(0, n, chunk):
         S = min(chunk, n - s0)
-        _call("ica_blur_sweep", ptr(x), ptr(wx[s0:]), ptr(wy[s0:]), S, B, H, W, kx, ky, float(factor * noise), s0,
+        call("ica_blur_sweep", ptr(x), ptr(wx[s0:]), ptr(wy[s0:]), S, B, H, W, kx, ky, float(factor * noise), s0,
               ptr(mse), n, ptr(idx), ptr(done), ptr(remaining), ptr(ws), stream())
         if int(remaining.item()) == 0:   # the one host read per chunk
             break
@@ -150,7 +136,7 @@ def blur_to_budget(x, noise, ksize=SWEEP_KSIZE, factor=SWEEP_FACTOR, start=SIGMA
     """generate_blurimages per image: (clamped blur at the first sigma of the schedule with mse <= factor * noise,
     sigma [B] float64, index [B] int32, mse [B]).  An image no candidate fits has index -1, sigma NaN, and comes back
     unchanged with mse 0."""
-    B, H, W = _check_image(x)
+    B, H, W = K.check_image(x, "x")
     validate(H, W, tuple(ksize), BLUR_SIGMA, noise, factor, start, step)
     sched = sigma_schedule(start, step)
     idx, _ = blur_sweep(x, sched, noise, ksize, factor)
@@ -168,7 +154,7 @@ def blur_to_budget(x, noise, ksize=SWEEP_KSIZE, factor=SWEEP_FACTOR, start=SIGMA
 
 def apply_noise(im, noise):
     """(clamp(im + noise, 0, 1), mean(noise^2) [B], mean((im_in - im)^2) [B])."""
-    B, H, W = _check_image(im, "im")
+    B, H, W = K.check_image(im, "im")
     if noise.shape != im.shape:
         raise ValueError(f"noise {tuple(noise.shape)} differs from im {tuple(im.shape)}")
     K._dev_check(noise, "noise")
@@ -178,7 +164,7 @@ def apply_noise(im, noise):
     power = torch.empty(B, dtype=torch.float32, device=im.device)
     mse_in = torch.empty(B, dtype=torch.float32, device=im.device)
     ws = _ws("ica_noise_apply_ws_size", B, H, W, im.device)
-    _call("ica_noise_apply", ptr(im), ptr(noise), ptr(im_in), B, H, W, ptr(power), ptr(mse_in), ptr(ws), stream())
+    call("ica_noise_apply", ptr(im), ptr(noise), ptr(im_in), B, H, W, ptr(power), ptr(mse_in), ptr(ws), stream())
     return im_in, power, mse_in
 
 
@@ -214,7 +200,7 @@ def evaluate_noise(kern, im, noise, num_pixels=None):
     """test (random_noise.py:68-111) per image: one eval forward over [im; im_in].  ``num_pixels`` (an int or one per
     image) is the unpadded H * W that bpp is divided by; the padded size if None."""
     from .attack import eval_forward
-    B, H, W = _check_image(im, "im")
+    B, H, W = K.check_image(im, "im")
     im_in, power, mse_in = apply_noise(im, noise)
     out, bpp = eval_forward(kern, torch.cat([im, im_in], 0), True)
     x_hat_ori, x_hat = out[:B].contiguous(), out[B:].contiguous()
@@ -236,7 +222,7 @@ def evaluate_deblur(kern, im_blur, im_sharp):
     """test_deblur (random_noise.py:38-48) per image, on the unclamped x_hat; bpp over the padded H * W the
     reference divides by (:38)."""
     from .attack import eval_forward
-    _check_image(im_blur, "im_blur")
+    K.check_image(im_blur, "im_blur")
     if im_sharp.shape != im_blur.shape:
         raise ValueError(f"im_sharp {tuple(im_sharp.shape)} differs from im_blur {tuple(im_blur.shape)}")
     K._dev_check(im_sharp, "im_sharp")

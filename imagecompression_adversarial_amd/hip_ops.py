@@ -121,6 +121,30 @@ def _dev_check(t: torch.Tensor, name="tensor"):
         raise RuntimeError(f"{name} must be contiguous")
 
 
+def check_image(x, name, dev=True):
+    """(B, H, W) of a planar [B, 3, H, W] batch: ValueError for anything else, then _dev_check (dev=False leaves the
+    tensor checks to a caller that orders them itself)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+        shape = tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"{name} {shape} is not a [B, 3, H, W] batch")
+    if dev:
+        _dev_check(x, name)
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+def check_nc4(x, name):
+    """(B, H, W) of a 3-channel nChw4c batch [B, 1, H, W, 4], checked like check_image."""
+    if x.dim() != 5 or x.shape[1] != 1 or x.shape[4] != 4 or x.shape[0] < 1:
+        raise ValueError(f"{name} {tuple(x.shape)} is not a 3-channel nChw4c batch [B, 1, H, W, 4]")
+    _dev_check(x, name)
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+def positive_int(name, v):
+    if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+        raise ValueError(f"{name} must be a positive int, got {v!r}")
+
+
 def c4(C: int) -> int:
     return (C + 3) // 4
 

@@ -17,21 +17,19 @@ import os
 import torch
 
 from . import hip_ops as K
-from ._lib import lib, ptr, stream
+from ._lib import call, ptr, stream
 
 
-def _call(name, C, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc == -2:
-        raise ValueError(f"{name}: C = {C} channels must be a multiple of 4 (whole nChw4c channel quads)")
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with status {rc}")
+def _quads_check(C):
+    if C < 1 or C % 4:   # the entry points' status -2
+        raise ValueError(f"C = {C} channels must be a positive multiple of 4 (whole nChw4c channel quads)")
 
 
 def _y4_check(y4, C, name="y4"):
     K._dev_check(y4, name)
     if y4.dim() != 5 or y4.shape[4] != 4 or y4.shape[1] != K.c4(C):
         raise ValueError(f"{name} {tuple(y4.shape)} is not an nChw4c tensor of {C} channels")
+    _quads_check(C)
 
 
 class RangeProfile:
@@ -87,7 +85,7 @@ def latent_range(y4, C, absmax=True):
     _y4_check(y4, C)
     B, _, H, W, _ = y4.shape
     out = torch.empty((3 if absmax else 2, B, C), dtype=torch.float32, device=y4.device)
-    _call("ica_latent_range", C, ptr(y4), B, C, H, W, ptr(out[0]), ptr(out[1]), ptr(out[2]) if absmax else None,
+    call("ica_latent_range", ptr(y4), B, C, H, W, ptr(out[0]), ptr(out[1]), ptr(out[2]) if absmax else None,
           stream())
     return (out[0], out[1], out[2]) if absmax else (out[0], out[1], None)
 
@@ -111,7 +109,7 @@ def latent_clamp(y4, C, profile, out=None, count=False):
             raise ValueError("out must have y4's shape")
     B, _, H, W, _ = y4.shape
     n = torch.empty(B, dtype=torch.int32, device=y4.device) if count else None
-    _call("ica_latent_clamp", C, ptr(y4), ptr(cmax), ptr(cmin), ptr(out), B, C, H, W, ptr(n), stream())
+    call("ica_latent_clamp", ptr(y4), ptr(cmax), ptr(cmin), ptr(out), B, C, H, W, ptr(n), stream())
     return (out, n) if count else out
 
 
@@ -123,7 +121,7 @@ def latent_clamp_bwd_(g4, y4, C, profile):
         raise ValueError("g4 must have y4's shape")
     cmax, cmin = _bounds(profile, C, y4.device)
     B, _, H, W, _ = y4.shape
-    _call("ica_latent_clamp_bwd", C, ptr(g4), ptr(y4), ptr(cmax), ptr(cmin), B, C, H, W, stream())
+    call("ica_latent_clamp_bwd", ptr(g4), ptr(y4), ptr(cmax), ptr(cmin), B, C, H, W, stream())
     return g4
 
 
@@ -135,8 +133,9 @@ def latent_detect(imax, imin, profile):
         raise ValueError(f"imax {tuple(imax.shape)} / imin {tuple(imin.shape)} must both be [B][C]")
     B, C = imax.shape
     cmax, cmin = _bounds(profile, C, imax.device)
+    _quads_check(C)
     score = torch.empty(B, dtype=torch.float32, device=imax.device)
-    _call("ica_latent_detect", C, ptr(imax), ptr(imin), ptr(cmax), ptr(cmin), ptr(score), B, C, stream())
+    call("ica_latent_detect", ptr(imax), ptr(imin), ptr(cmax), ptr(cmin), ptr(score), B, C, stream())
     return score
 
 

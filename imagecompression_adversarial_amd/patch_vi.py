@@ -17,7 +17,7 @@ from dataclasses import dataclass
 import torch
 
 from . import hip_ops as K
-from ._lib import lib, ptr, stream
+from ._lib import call, lib, ptr, stream
 
 WIN, STRIDE, BORDER = 64, 2, 10   # attack_patch.py:121, :137-140
 
@@ -49,22 +49,14 @@ def validate(H, W, win=WIN, stride=STRIDE, border=BORDER):
 
 
 def _check_inputs(im_adv, out_adv, im_s, out_s, win, stride, border):
-    if im_adv.dim() != 4 or im_adv.shape[1] != 3 or im_adv.shape[0] < 1:
-        raise ValueError(f"im_adv {tuple(im_adv.shape)} is not a [B, 3, H, W] batch")
+    B, H, W = K.check_image(im_adv, "im_adv", dev=False)   # validate() runs before the device checks
     for name, t in (("out_adv", out_adv), ("im_s", im_s), ("out_s", out_s)):
         if t.shape != im_adv.shape:
             raise ValueError(f"{name} {tuple(t.shape)} differs from im_adv {tuple(im_adv.shape)}")
-    B, _, H, W = im_adv.shape
     validate(H, W, win, stride, border)
     for name, t in (("im_adv", im_adv), ("out_adv", out_adv), ("im_s", im_s), ("out_s", out_s)):
         K._dev_check(t, name)
     return B, H, W
-
-
-def _call(name, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with status {rc}")
 
 
 @dataclass
@@ -100,7 +92,7 @@ def local_vi(im_adv, out_adv, im_s, out_s, win=WIN, stride=STRIDE, border=BORDER
     pos = torch.empty((B, 2), dtype=torch.int32, device=dev)
     ws = torch.empty(lib().ica_patch_vi_ws_size(B, H, W, win, stride), dtype=torch.float32, device=dev)
     key = torch.empty(B, dtype=torch.int64, device=dev)
-    _call("ica_patch_vi", ptr(im_adv), ptr(out_adv), ptr(im_s), ptr(out_s), B, H, W, win, stride, border, ptr(ws),
+    call("ica_patch_vi", ptr(im_adv), ptr(out_adv), ptr(im_s), ptr(out_s), B, H, W, win, stride, border, ptr(ws),
           ptr(key), ptr(maps[0]), ptr(maps[1]), ptr(maps[2]), ptr(val), ptr(pos), stream())
     return LocalVI(maps[0], maps[1], maps[2], val, pos, win, stride, border)
 
@@ -114,7 +106,7 @@ def worst_patches(im_adv, out_adv, im_s, out_s, win=WIN, stride=STRIDE, border=B
     if not pos.is_cuda or pos.dtype != torch.int32 or tuple(pos.shape) != (B, 2) or not pos.is_contiguous():
         raise ValueError("pos must be a contiguous int32 [B, 2] tensor on the device")
     patches = torch.empty((B, 4, 3, win, win), dtype=torch.float32, device=im_adv.device)
-    _call("ica_patch_gather", ptr(im_adv), ptr(out_adv), ptr(im_s), ptr(out_s), ptr(pos), ptr(patches), B, H, W, win,
+    call("ica_patch_gather", ptr(im_adv), ptr(out_adv), ptr(im_s), ptr(out_s), ptr(pos), ptr(patches), B, H, W, win,
           stride, stream())
     return patches
 

@@ -30,7 +30,7 @@ from dataclasses import dataclass
 import torch
 
 from . import hip_ops as K
-from ._lib import lib, ptr, stream
+from ._lib import call, lib, ptr, stream
 
 LIK_FLOOR = 1.0 / 65536           # train.py:62
 MSSSIM_MIN_SIDE = 160             # pytorch_msssim: min(H, W) > (11 - 1) * 2^4
@@ -39,28 +39,18 @@ MSSSIM_MIN_SIDE = 160             # pytorch_msssim: min(H, W) > (11 - 1) * 2^4
 def validate(im, generations=1, check_every=8):
     """ValueError unless ``im`` is a [B, 3, H, W] contiguous fp32 device tensor with H, W multiples of 64 (as
     coder.read_image pads it) and the counts are positive ints.  Runs before anything is launched."""
-    if not isinstance(im, torch.Tensor) or im.dim() != 4 or im.shape[1] != 3 or im.shape[0] < 1:
-        shape = tuple(im.shape) if isinstance(im, torch.Tensor) else type(im).__name__
-        raise ValueError(f"im {shape} is not a [B, 3, H, W] batch")
+    B, H, W = K.check_image(im, "im", dev=False)   # the tensor checks below are ValueErrors, the device check last
     if im.dtype != torch.float32:
         raise ValueError(f"im must be float32, got {im.dtype}")
     if not im.is_contiguous():
         raise ValueError("im must be contiguous")
-    H, W = im.shape[2:]
     if H % 64 or W % 64:
         raise ValueError(f"H x W = {H} x {W} must be multiples of 64 (coder.read_image's padding)")
-    for name, v in (("generations", generations), ("check_every", check_every)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    K.positive_int("generations", generations)
+    K.positive_int("check_every", check_every)
     if not im.is_cuda:
         raise ValueError("im must be a HIP device tensor (no CPU fallback)")
-    return im.shape[0], H, W
-
-
-def _call(name, *args):
-    rc = getattr(lib(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with status {rc}")
+    return B, H, W
 
 
 def quant8_pack(im):
@@ -69,7 +59,7 @@ def quant8_pack(im):
     K._dev_check(im, "im")
     q = torch.empty((B, H, W), dtype=torch.int32, device=im.device)
     x4 = K.empty_nc4(B, 3, H, W, im.device)
-    _call("ica_quant8_pack", ptr(im), B, H, W, ptr(x4), ptr(q), stream())
+    call("ica_quant8_pack", ptr(im), B, H, W, ptr(x4), ptr(q), stream())
     return q, x4
 
 
@@ -87,7 +77,7 @@ def requant8(x_hat4, orig, prev_q, next4=None, q=None, out=None, sse_orig=None, 
     changed = torch.empty(B, dtype=torch.int64, device=dev) if changed is None else changed
     if ws is None:
         ws = torch.empty(lib().ica_requant8_ws_size(B, H, W), device=dev)
-    _call("ica_requant8", ptr(x_hat4), ptr(orig), ptr(prev_q), B, H, W, ptr(next4), ptr(q), ptr(out), ptr(sse_orig),
+    call("ica_requant8", ptr(x_hat4), ptr(orig), ptr(prev_q), B, H, W, ptr(next4), ptr(q), ptr(out), ptr(sse_orig),
           ptr(sse_gen), ptr(changed), ptr(moving), ptr(ws), stream())
     return next4, q, sse_orig, sse_gen, changed
 
@@ -98,7 +88,7 @@ def floor_bits(lik4, C, floor=LIK_FLOOR, out=None):
     B, _, H, W, _ = lik4.shape
     out = torch.empty(B, device=lik4.device) if out is None else out
     ws = torch.empty(lib().ica_floor_bits_ws_size(B, C, H, W), device=lik4.device)
-    _call("ica_floor_bits", ptr(lik4), B, C, H, W, float(floor), ptr(out), ptr(ws), stream())
+    call("ica_floor_bits", ptr(lik4), B, C, H, W, float(floor), ptr(out), ptr(ws), stream())
     return out
 
 

@@ -26,25 +26,11 @@ from ._lib import call, lib, ptr, stream
 GUARD = 1e-20          # attack.evaluate: a ratio is formed only where both means exceed it
 
 
-def _check_image(x, name):
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-        raise ValueError(f"{name} {tuple(x.shape)} is not a [B, 3, H, W] batch")
-    K._dev_check(x, name)
-    return x.shape[0], x.shape[2], x.shape[3]
-
-
-def _check_nc4(x, name):
-    if x.dim() != 5 or x.shape[1] != 1 or x.shape[4] != 4 or x.shape[0] < 1:
-        raise ValueError(f"{name} {tuple(x.shape)} is not a 3-channel nChw4c batch [B, 1, H, W, 4]")
-    K._dev_check(x, name)
-    return x.shape[0], x.shape[2], x.shape[3]
-
-
 def apply_pairs(im, noise):
     """im [M, 3, H, W], noise [N, 3, H, W] -> (im_in [N M, 3, H, W] with pair (i, j) at i M + j,
     mse_in [N, M] = mean((im_in - im[j])^2))."""
-    M, H, W = _check_image(im, "im")
-    N, Hn, Wn = _check_image(noise, "noise")
+    M, H, W = K.check_image(im, "im")
+    N, Hn, Wn = K.check_image(noise, "noise")
     if (Hn, Wn) != (H, W):
         raise ValueError(f"noise {tuple(noise.shape)} and im {tuple(im.shape)} differ in size")
     if W % 4:
@@ -62,11 +48,10 @@ def apply_pairs(im, noise):
 def score_pairs(x_hat4, x_s4, N, M, clamp=True):
     """x_hat4 [N M, 1, H, W, 4] (the decoder's output of the pair batch), x_s4 [M, 1, H, W, 4] (of the clean
     targets) -> mse_out [N, M] over the 3 real channels, both operands clamped to [0, 1] if ``clamp``."""
-    for name, v in (("N", N), ("M", M)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise ValueError(f"{name} must be a positive int, got {v!r}")
-    B, H, W = _check_nc4(x_hat4, "x_hat4")
-    Ms, Hs, Ws = _check_nc4(x_s4, "x_s4")
+    K.positive_int("N", N)
+    K.positive_int("M", M)
+    B, H, W = K.check_nc4(x_hat4, "x_hat4")
+    Ms, Hs, Ws = K.check_nc4(x_s4, "x_s4")
     if Ms != M or B != N * M:
         raise ValueError(f"x_hat4 holds {B} and x_s4 {Ms} images, not {N} x {M} pairs and {M} targets")
     if (Hs, Ws) != (H, W):
@@ -84,8 +69,7 @@ def pair_chunks(N, M, batch):
     """[((i0, i1), (j0, j1))]: targets in runs of at most ``batch``; per run max(1, batch // run) noises at a time.
     Every pair lies in exactly one block and no block holds more than ``batch`` pairs."""
     for name, v in (("N", N), ("M", M), ("batch", batch)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-            raise ValueError(f"{name} must be a positive int, got {v!r}")
+        K.positive_int(name, v)
     out = []
     for j0 in range(0, M, batch):
         j1 = min(j0 + batch, M)
@@ -112,8 +96,8 @@ def transfer_matrix(kern, noises, images, batch=32, clamp=True):
     """Noise i on image j for noises [N, 3, H, W] and images [M, 3, H, W] of one padded size.  Each run of targets is
     coded clean once and its x_hat4 kept for every noise chunk; a chunk is one apply_pairs, one forward of at most
     ``batch`` images, one score_pairs and one host read."""
-    M, H, W = _check_image(images, "images")
-    N, Hn, Wn = _check_image(noises, "noises")
+    M, H, W = K.check_image(images, "images")
+    N, Hn, Wn = K.check_image(noises, "noises")
     if (Hn, Wn) != (H, W):
         raise ValueError(f"noises {tuple(noises.shape)} and images {tuple(images.shape)} differ in size")
     chunks = pair_chunks(N, M, batch)
@@ -170,7 +154,7 @@ def cross_model_matrix(kerns, attack_fn, images, batch=32):
     groups = [images] if torch.is_tensor(images) else list(images)
     chunks = []
     for g in groups:
-        B, _, _ = _check_image(g, "images")
+        B, _, _ = K.check_image(g, "images")
         chunks += [g[b0:b0 + batch] for b0 in range(0, B, batch)]
     nk = len(kerns)
     adv = [[attack_fn(kern, im_s).contiguous() for im_s in chunks] for kern in kerns]
