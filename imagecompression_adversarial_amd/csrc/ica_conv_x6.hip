@@ -22,6 +22,7 @@
 //                  each wave runs two classes (9 + 4 or 6 + 6 taps) over 2 pixel tiles.
 // One block per CU (the 3-plane patches take 122 / 138 KB of LDS), so each wave has the whole 512-register file.
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "ica_conv_epi.h"
@@ -33,16 +34,23 @@ constexpr int XD_TW = 32;
 // conv_down_x6 rows per block: 4 waves x PT tiles of one 32-pixel row each.  PT = 1 (128-pixel blocks, 71 KB of LDS)
 // where the PT = 2 grid (256-pixel blocks, one per CU) would leave CUs idle (the fine-tune's 64 x 64 layers: 128
 // blocks for 256 CUs).  Both run the same MFMA sequence per output.
-template <int PT>
-constexpr int xd_th() { return 4 * PT; }
+template <int PT, int CS = 1>
+constexpr int xd_th() { return CS == 1 ? 4 * PT : 4; }
+// CS = 2 (conv_down_x6 over both channel blocks of a 2 IT x 32-channel layer): the block is 4 output rows x 16 PT
+// columns; waves (wave & 1, wave >> 1) = (row pair, channel block), each PT tiles of 2 rows x 16 columns.  At PT = 3
+// a 48-wide map is covered without a partly empty column tile (the 32-wide row tiles compute 64 columns for 48), and
+// the 128 -> 192 layers of a 32 x 48 latent at B = 32 are 256 blocks: one per CU, one round.
+template <int PT, int CS = 1>
+constexpr int xd_tw() { return CS == 1 ? XD_TW : 16 * PT; }
 
 // --------------------------------------------------------------------------------------------------------------
 // conv_down_x6: weights [plane][cb][chunk][tap][it][lane] bf16x8 (plane stride ps fragments)
 // --------------------------------------------------------------------------------------------------------------
-template <int IT, int EPI, int PT = X6_PT>
+template <int IT, int EPI, int PT = X6_PT, int CS = 1>
 __global__ __launch_bounds__(256, 1) void conv_down_x6_kernel(ConvParams p, long ps) {
   ICA_STAMP_BEGIN();
-  constexpr int KS = 5, S = 2, PAD = 2, KK = 25, TW = XD_TW, TH = xd_th<PT>();
+  static_assert(CS == 1 || (CS == 2 && EPI == EPI_BIAS), "conv_down_x6 over two channel blocks: bias epilogue only");
+  constexpr int KS = 5, S = 2, PAD = 2, KK = 25, TW = xd_tw<PT, CS>(), TH = xd_th<PT, CS>();
   constexpr int PR = S * (TH - 1) + KS, PC = S * (TW - 1) + KS, PLANE = PR * PC;
   constexpr int NF = (4 * PLANE + 255) / 256, NB = (NF + 1) / 2;  // fill items per thread, in two batches
   __shared__ f32x4 patch[3 * 2 * PLANE];                          // [plane][half][pixel]: 8 channels as bf16
@@ -54,6 +62,10 @@ __global__ __launch_bounds__(256, 1) void conv_down_x6_kernel(ConvParams p, long
   const int ty = bid % tiles_y;
   const int n = bid / tiles_y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, j = lane & 31;
+  if constexpr (CS == 2) cb = __builtin_amdgcn_readfirstlane(wave >> 1);   // grid.y = 1: the wave's channel block
+  // lane j's output pixel of this wave's tile t, relative to the block
+  auto trow = [&](int t) { return CS == 1 ? wave * PT + t : 2 * (wave & 1) + (j >> 4); };
+  auto tcol = [&](int t) { return CS == 1 ? j : 16 * t + (j & 15); };
   const int oy0 = ty * TH, ox0 = tx * TW;
   const int iy0 = oy0 * S - PAD, ix0 = ox0 * S - PAD;
   const int Cin4 = (p.Cin + 3) >> 2, nch = (Cin4 * 4 + 15) / 16;
@@ -116,7 +128,7 @@ __global__ __launch_bounds__(256, 1) void conv_down_x6_kernel(ConvParams p, long
     const int ky = tap / 5, kx = tap - ky * 5;
 #pragma unroll
     for (int t = 0; t < PT; ++t) {
-      const int o = h * PLANE + (S * (wave * PT + t) + ky) * PC + S * j + kx;
+      const int o = h * PLANE + (S * trow(t) + ky) * PC + S * tcol(t) + kx;
       const bf16x8 b[3] = {f4_as_bf8(patch[o]), f4_as_bf8(patch[2 * PLANE + o]), f4_as_bf8(patch[4 * PLANE + o])};
 #pragma unroll
       for (int it = 0; it < IT; ++it) acc[t][it] = mfma_x6(cur[it], b, acc[t][it]);
@@ -164,7 +176,7 @@ __global__ __launch_bounds__(256, 1) void conv_down_x6_kernel(ConvParams p, long
   } else {
 #pragma unroll
     for (int t = 0; t < PT; ++t) {
-      const int oy = oy0 + wave * PT + t, ox = ox0 + j;
+      const int oy = oy0 + trow(t), ox = ox0 + tcol(t);
       conv_epilogue<IT, EPI, 0, false, 1>(p, acc[t], n, oy, ox, oy < p.Hout && ox < p.Wout, cb * IT * 32);
     }
   }
@@ -2245,6 +2257,37 @@ int launch_down_x6w(const ConvParams& p, hipStream_t st) {
   return 0;
 }
 
+// conv_down_x6 over both channel blocks (CS = 2, PT = 3): blocks of 4 rows x 48 columns x 2 IT x 32 channels
+template <int IT, int EPI>
+int launch_down_x6_cs2(const ConvParams& p, hipStream_t st) {
+  constexpr int PT = 3;
+  const int tiles = ((p.Wout + xd_tw<PT, 2>() - 1) / xd_tw<PT, 2>()) * ((p.Hout + xd_th<PT, 2>() - 1) / xd_th<PT, 2>()) * p.N;
+  if (p.Cout != 2 * IT * 32) return -3;
+  const long ps = 2L * ((((p.Cin + 3) / 4) * 4 + 15) / 16) * 25 * IT * 64;
+  ICA_LAUNCH((conv_down_x6_kernel<IT, EPI, PT, 2>), dim3(tiles, 1), dim3(256), 0, st, p, ps);
+  ICA_CHECK_LAUNCH();
+  return 0;
+}
+
+// fraction of the launch's rounds of 256 one-per-CU blocks that is busy
+static inline double x6_round_fill(long blocks) {
+  const long rounds = (blocks + 255) / 256;
+  return rounds ? (double)blocks / (double)(rounds * 256) : 1.0;
+}
+static inline long x6_rounds(long blocks) { return (blocks + 255) / 256; }
+
+// Tiling override for tests and A/B runs (ica_x6_tiling): 0 = the pickers below; 1 = the large-grid kernel each layer
+// ran before it had a second one (conv_down: 8 x 32-pixel blocks at PT = 2; conv_up: PT = 1, forward layers on four
+// waves) whatever its grid; 2 = the newer one wherever the layer has it (launch_down_x6_cs2; conv_up: PT = 1, forward
+// layers of 64-channel groups on eight waves).  Modes 1 and 2 also skip the small-grid rule, so a few-pixel map can
+// run the large-grid kernels.  The large-grid kernels of a layer give the same bits as each other; the small-grid
+// kernels split the K loop over the waves and sum in another order, so a map of <= 32 x 32 pixels under mode 1 or 2
+// agrees with mode 0 to fp32 rounding, not bit for bit.  Nothing but tests and A/B scripts sets it: the attack, the
+// trainers and bench.py always run mode 0.  Each launch reads it once (relaxed atomic: a setter on another thread
+// changes later launches, never one half-way through its picker).
+std::atomic<int> g_x6_tiling{0};
+static inline int x6_tiling_mode() { return g_x6_tiling.load(std::memory_order_relaxed); }
+
 constexpr int XS_SMALL_PX = 32 * 32;   // the small-grid x6 kernels: low-resolution side <= 32 x 32 per image
 
 template <int IT, int EPI>
@@ -2261,16 +2304,33 @@ int launch_down_small_x6(const ConvParams& p, hipStream_t st) {
 // batch size) take the small-grid kernel.  Otherwise PT = 1 when the PT = 2 grid would leave CUs idle (fewer
 // blocks than the 256 CUs): PT = 1 and PT = 2 run the same MFMA and epilogue sequence per output (same bits), so
 // this batch-dependent choice keeps every image's result.
+//   The 192-channel bias layers (IT = 3, two channel blocks: g_a.6 forward, the g_s.0 input gradient) also have the
+// 4 x 48-pixel tiling over both channel blocks (launch_down_x6_cs2).  A block of it runs 3 x IT tile products per
+// wave where the PT = 2 block runs 2 x IT, so it is taken when its rounds x 3 undercut the PT = 2 grid's rounds x 2
+// and its block count fills those rounds to 95 % (config 2's 32 x 48 latents at B = 32: 256 blocks, one round x 3,
+// against 512 blocks, two rounds x 2, a quarter of whose columns are padding).  Same MFMA and epilogue sequence per
+// output: same bits.
 template <int IT, int EPI>
 int launch_down_x6(const ConvParams& p, hipStream_t st) {
-  if (p.Hout * p.Wout <= XS_SMALL_PX) return launch_down_small_x6<IT, EPI>(p, st);
+  constexpr bool CS2 = IT == 3 && EPI == EPI_BIAS;
+  const int mode = x6_tiling_mode();
+  if constexpr (CS2) {
+    if (mode == 2 && p.Cout == 2 * IT * 32) return launch_down_x6_cs2<IT, EPI>(p, st);
+  }
+  if (p.Hout * p.Wout <= XS_SMALL_PX && mode == 0) return launch_down_small_x6<IT, EPI>(p, st);
   const int blocks2 = ((p.Wout + XD_TW - 1) / XD_TW) * ((p.Hout + xd_th<X6_PT>() - 1) / xd_th<X6_PT>()) * p.N *
                       ((p.Cout + IT * 32 - 1) / (IT * 32));
   if constexpr (IT == 4) {   // 128 output channels: the 8-wave kernel
-    if (blocks2 < 256) return launch_down_x6w<EPI, 1>(p, st);
+    if (blocks2 < 256 && mode == 0) return launch_down_x6w<EPI, 1>(p, st);
     return launch_down_x6w<EPI, 2>(p, st);
   }
+  if (mode == 1) return launch_down_x6_pt<IT, EPI, X6_PT>(p, st);
   if (blocks2 < 256) return launch_down_x6_pt<IT, EPI, 1>(p, st);
+  if constexpr (CS2) {
+    const long bcs = (long)((p.Wout + xd_tw<3, 2>() - 1) / xd_tw<3, 2>()) * ((p.Hout + xd_th<3, 2>() - 1) / xd_th<3, 2>()) * p.N;
+    if (p.Cout == 2 * IT * 32 && x6_round_fill(bcs) >= 0.95 && 3 * x6_rounds(bcs) < 2 * x6_rounds(blocks2))
+      return launch_down_x6_cs2<IT, EPI>(p, st);
+  }
   return launch_down_x6_pt<IT, EPI, X6_PT>(p, st);
 }
 
@@ -2365,12 +2425,6 @@ int launch_up_x6w(const ConvParams& p, hipStream_t st) {
   return 0;
 }
 
-// fraction of the launch's last round of 256 one-per-CU blocks that is busy, over all rounds
-static inline double x6_round_fill(long blocks) {
-  const long rounds = (blocks + 255) / 256;
-  return rounds ? (double)blocks / (double)(rounds * 256) : 1.0;
-}
-
 // PT = 1 when the PT = 2 grid leaves a partly-empty last round and halving the blocks fills the rounds clearly
 // better (config 2's 32x48-input layers: 384 blocks = 1.5 rounds -> 768 = 3 rounds); same bits either way
 template <int IT, int EPI, int CG>
@@ -2390,8 +2444,18 @@ int launch_up_x6(const ConvParams& p, hipStream_t st) {
 #else
   constexpr bool SLAB = BWD && IT == 4 && CG == 64;
 #endif
-  if (x6_round_fill(b1) > x6_round_fill(b2) + 0.15) {
+  // PT = 1 forward layers on 64-channel groups (Cin = 192: g_s.0) also take the 8-wave kernel.  On four waves a
+  // wave runs its two classes one after the other and each re-stages every group: 6 fills between barriers per block;
+  // on eight, one class per wave, each group is staged once (3 fills) and the SIMD partner covers the waits.  Same
+  // grid (768 blocks at config 2's 32 x 48 latents), same bits; g_s.0.fwd 0.391 -> 0.311 ms per step in bench.py
+  // --full (DESIGN §7 "Latent-end tilings", profiles/latent_end_tiles/*_bench_full.json).  Whole-Cin (CG = 128)
+  // PT = 1 layers keep the 4-wave kernel (not measured).  The override modes run PT = 1 whatever the grid.
+  const int mode = x6_tiling_mode();
+  if (mode != 0 || x6_round_fill(b1) > x6_round_fill(b2) + 0.15) {
     if constexpr (SLAB) return launch_up_x6w<IT, EPI, CG, 1>(p, st);
+    if constexpr (IT == 4 && !BWD && CG == 64) {
+      if (mode != 1) return launch_up_x6w<IT, EPI, CG, 1>(p, st);
+    }
     return launch_up_x6_pt<IT, EPI, CG, 1>(p, st);
   }
   // the 8-wave class-per-wave kernel: forward layers (bias / IGDN) and the slab GDN backward
@@ -2460,7 +2524,8 @@ int launch_up_small_x6(const ConvParams& p, hipStream_t st) {
 
 template <int IT, int EPI>
 int pick_up_x6(const ConvParams& p, hipStream_t st) {
-  if (p.Hin * p.Win <= XS_SMALL_PX && p.Cin >= 64 && p.Cin % 16 == 0) return launch_up_small_x6<IT, EPI>(p, st);
+  if (p.Hin * p.Win <= XS_SMALL_PX && p.Cin >= 64 && p.Cin % 16 == 0 && x6_tiling_mode() == 0)
+    return launch_up_small_x6<IT, EPI>(p, st);
   if (p.Cin <= 128 && p.Cin % 16 == 0) {
     if (p.Cin == 128) return launch_up_x6<IT, EPI, 128>(p, st);
     if (p.Cin == 64) return launch_up_x6<IT, EPI, 64>(p, st);
@@ -2555,6 +2620,13 @@ int ica_conv_x6_dispatch(const ConvParams& p, int kind, int KS, int S, int it, i
 }
 
 extern "C" {
+
+// which tiling the x6 pickers take (g_x6_tiling above): 0 the pickers' own choice, 1 / 2 for tests and A/B runs
+int ica_x6_tiling(int mode) {
+  if (mode < 0 || mode > 2) return -2;
+  g_x6_tiling.store(mode, std::memory_order_relaxed);
+  return 0;
+}
 
 size_t ica_pack_conv_weight_x6_size(int O, int C, int KS, int IT) {
   // the 16-channel-chunk pack, plus (KS = 5, IT = 4) the tap-pair pack of conv_down_x6w behind it

@@ -87,6 +87,20 @@ def last_launch():
     return buf.value.decode(errors="replace"), int(thr.value)
 
 
+X6_TILING_AUTO, X6_TILING_PREVIOUS, X6_TILING_BALANCED = 0, 1, 2
+
+
+def x6_tiling(mode: int = X6_TILING_AUTO) -> None:
+    """Which tiling the x6 k5 s2 pickers take (ica_x6_tiling; process-wide, for tests and A/B runs): AUTO = their own
+    choice from the grid; PREVIOUS = the large-grid kernel a layer ran before it had a second one (conv_down: 8 x 32
+    blocks, conv_up: PT = 1 with forward layers on four waves); BALANCED = the newer one wherever a layer has it
+    (conv_down 128 -> 192: 4 x 48 blocks over both channel blocks; conv_up forward from 192 channels: eight waves).
+    Both also skip the small-grid kernels.  The large-grid kernels of a layer give the same bits as each other; the
+    small-grid kernels sum in another order, so on maps of <= 32 x 32 pixels PREVIOUS / BALANCED match AUTO to fp32
+    rounding, not bit for bit.  Nothing in the package sets it: leave it at AUTO outside tests."""
+    call("ica_x6_tiling", int(mode))
+
+
 # operand precision of each tagged conv launch (filled while EVENT_HOOK is set): what actually ran, small-grid
 # fp32 fallbacks of x6 layers included
 PREC_HOOK = {}

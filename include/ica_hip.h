@@ -260,6 +260,13 @@ int ica_conv_ex(const ica_conv_args* args, hipStream_t stream);
  * bench.py matches its PMC traffic stamps (profiles/pmc_traffic*.json) against the launch it timed, and only when the
  * timed region held exactly one launch. */
 int ica_last_launch(char* name, int cap, unsigned long long* threads);
+/* Tiling the x6 k5 s2 pickers take (process-wide; for tests and A/B runs): 0 = their own choice from the grid (the
+ * default), 1 = the large-grid kernel a layer ran before it had a second one, whatever the grid, 2 = the newer one
+ * wherever a layer has it (ica_conv_x6.hip: g_x6_tiling); 1 and 2 skip the small-grid kernels.  The large-grid
+ * kernels of a layer give the same bits as each other; the small-grid kernels sum in another order, so for maps of
+ * <= 32 x 32 pixels modes 1 / 2 match mode 0 to fp32 rounding only.  Read once per launch (atomic); nothing in the
+ * package sets it.  Returns -2 for another mode. */
+int ica_x6_tiling(int mode);
 /* Transposed conv to 3 channels (Z-gather kernel): w view [Cin][3][5][5].  layout: 1 = x parity-split
  * (ica_conv_args.layout bit 0; even Hin / Win), 0 = row-major; the 3-channel output is always row-major. */
 size_t ica_pack_up3_size(int Cin);
