@@ -88,6 +88,9 @@ _SIGS = {
     "ica_latent_clamp": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p],
     "ica_latent_clamp_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ica_latent_detect": [_p, _p, _p, _p, _p, _i, _i, _p],
+    # latent distribution: per-channel histogram, predicted distribution, bits (ica_distrib.hip)
+    "ica_latent_distrib_ws_size": [_i, _i, _i, _i, _i],
+    "ica_latent_distrib": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _p, _p],
     # patch-wise VI localisation (ica_patch.hip)
     "ica_patch_vi_ws_size": [_i, _i, _i, _i, _i],
     "ica_patch_vi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
@@ -157,7 +160,7 @@ _RESTYPES = {"ica_pack_conv_weight_size": _sz, "ica_pack_conv_weight_bf16_size":
              "ica_rans_encode": _l, "ica_ar_lds_bytes": _sz, "ica_patch_vi_ws_size": _sz,
              "ica_gauss_blur_ws_size": _sz, "ica_blur_sweep_ws_size": _sz, "ica_noise_apply_ws_size": _sz,
              "ica_transfer_apply_ws_size": _sz, "ica_transfer_score_ws_size": _sz,
-             "ica_requant8_ws_size": _sz, "ica_floor_bits_ws_size": _sz}
+             "ica_requant8_ws_size": _sz, "ica_floor_bits_ws_size": _sz, "ica_latent_distrib_ws_size": _sz}
 
 
 

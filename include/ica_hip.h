@@ -396,6 +396,31 @@ int ica_latent_clamp_bwd(float* g4, const float* y4, const float* cmax, const fl
 int ica_latent_detect(const float* imax, const float* imin, const float* cmax, const float* cmin, float* score, int B,
                       int C, hipStream_t stream);
 
+/* ---- latent distribution (ica_distrib.hip) ----------------------------------
+ * visual_distribution.py's numbers for one batch, from the tensors of the eval forward: y4, scales4, means4 (NULL:
+ * mu = 0, the hyperprior model) and lik4 (NULL: no bits) are fp32 nChw4c [B][C/4][H][W][4], 16-byte aligned.  Bin k
+ * of nbins (1 .. 64) unit bins covers [vmin + k, vmin + k + 1), the last one closed on the right; vmax = vmin + nbins
+ * in fp32.
+ *   hist [B][C][nbins] int32 = torch.histc(y[b, c], nbins, vmin, vmax) of a float CPU tensor, exact counts:
+ *     pos = (int)(((v - vmin) * nbins) / (vmax - vmin)) in fp32, pos == nbins -> nbins - 1; values outside
+ *     [vmin, vmax], NaN and +-inf are skipped.  hist is zeroed first.
+ *   pred [B][C][nbins] = mean over (H, W) of max(cdf(vmin + k + 1) - cdf(vmin + k), pred_floor) with
+ *     cdf(v) = 0.5 * (1 + erff(((v - mu) * (1 / sigma)) / sqrt(2))), sigma = max(scale, scale_floor): the operation
+ *     order of torch.distributions.Normal.cdf (visual_distribution.py:85-101), in fp32.  The edge vmin + j is one
+ *     rounded fp32 sum: equal to the reference's (vmin + 0.5 + k) -/+ 0.5 when those sums are exact (integer or
+ *     half-integer vmin), within one ulp of the edge otherwise.
+ *   bits [B][C] (written only with lik4) = sum over (H, W) of -log2f(lik).
+ * work: scratch of ica_latent_distrib_ws_size floats (0 for an unsupported problem).  pred and bits are fixed-order
+ * sums over min(ceil(H * W / 256), 64) partials per row, a function of the plane alone: a row's numbers are the same
+ * bits alone and in a batch, run to run.  Status: 0; -2 unless C is a positive multiple of 4; -5 for nbins outside
+ * 1 .. 64, a non-finite vmin, B < 1, B * ceil(nbins / 16) > 65535, C > 4 * 65535, H * W > 2^29 - 1, B * C * H * W >= 2^47,
+ * more than 2^31 - 1 partials, a missing pointer or one that is not 16-byte aligned; -7 for an output that overlaps
+ * an input or another output.  Nothing is launched then. */
+size_t ica_latent_distrib_ws_size(int B, int C, int H, int W, int nbins);
+int ica_latent_distrib(const float* y4, const float* scales4, const float* means4, const float* lik4, int B, int C,
+                       int H, int W, float vmin, int nbins, float scale_floor, float pred_floor, int* hist,
+                       float* pred, float* bits, float* work, hipStream_t stream);
+
 /* ---- patch-wise VI localisation (ica_patch.hip) ----------------------------
  * psnr_partial (attack_patch.py:119-146) on four planar NCHW fp32 tensors [B][3][H][W], per image.  With
  * nh = (H - win) / stride + 1 and nw likewise: mse_in / mse_out [B][nh][nw] are the means over the 3 * win^2 window
