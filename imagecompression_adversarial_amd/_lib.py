@@ -91,6 +91,11 @@ _SIGS = {
     # latent distribution: per-channel histogram, predicted distribution, bits (ica_distrib.hip)
     "ica_latent_distrib_ws_size": [_i, _i, _i, _i, _i],
     "ica_latent_distrib": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _p, _p],
+    # bitrate attack: entropy-model value gradients (ica_rate.hip)
+    "ica_rate_gc_blocks": [],
+    "ica_rate_eb_blocks": [_i, _i, _i],
+    "ica_rate_gc": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
+    "ica_rate_eb": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
     # patch-wise VI localisation (ica_patch.hip)
     "ica_patch_vi_ws_size": [_i, _i, _i, _i, _i],
     "ica_patch_vi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],

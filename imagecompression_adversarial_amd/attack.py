@@ -22,6 +22,10 @@ output_s.  Same step loop, schedule, branch rule and per-image semantics as abov
 
 ``ifgsm_batch`` == attack_ifgsm.attack_ifgsm (attack_ifgsm.py:364-438) without
 random start (the reference default path), per image.
+
+``rate_attack_batch`` / ``RateAttackLoop`` give the bitrate attack (attack_rd -r; DESIGN.md "Rate attack"): the same
+loop with -bpp of the relaxed codec (zero-noise train-mode likelihoods of the unrounded latents) as the expensive
+branch's loss.  The reference parses -r and never reads it.
 """
 from __future__ import annotations
 
@@ -415,6 +419,113 @@ def attack_batch(kern: CodecKernels, im_s, steps=1001, epsilon=16.0, noise_thr=1
         res.output_t = loop.output_t
         res.tar_mse = roi_mse(out, loop.output_t, loop.roi[:4])
     return res
+
+
+RATE_MODELS = ("hyper", "factorized")
+
+
+def rate_attack_guard(model=None, precision=None, att_metric="L2", coupled=False, target=None, roi=None):
+    """What the bitrate attack does not cover, each with its reason (NotImplementedError).  Shared by RateAttackLoop
+    and the attack_rd CLI, which checks before it loads a model."""
+    if coupled:
+        raise NotImplementedError("the rate attack is per-image: the batch-coupled semantics belong to the "
+                                  "adversarial fine-tune's distortion attack")
+    if target is not None or roi is not None:
+        raise NotImplementedError("the rate attack has no target / ROI form: its loss is the whole image's bitrate")
+    if att_metric != "L2":
+        raise NotImplementedError(f"the rate attack's input budget is the L2 one (att_metric {att_metric!r}): its "
+                                  "cheap branch is the L2 input loss, its expensive branch uses no image metric")
+    if precision == "bf16":
+        raise NotImplementedError("the rate attack runs fp32 / x6 operands: the entropy models read an fp32 latent")
+    if model is not None and model not in RATE_MODELS:
+        raise NotImplementedError(f"the rate attack covers {RATE_MODELS}, not {model!r}: the rounding inside the "
+                                  "context models (and the debug model's mean-scale prior) has no stated relaxation")
+
+
+class RateAttackLoop(AttackLoop):
+    """attack_rd -r: the attack_rd.attack_ loop with the bitrate as the expensive branch's loss.  Per image,
+
+        y = g_a(im_in)                                              (no rounding, no noise)
+        hyper:      z = h_a(|y|); lik_z = EB(z); sigma = h_s(z); lik_y = GC(y, sigma)
+        factorized: lik_y = EB(y)
+        loss_o = sum(ln lik) / (ln 2 * H * W) = -bpp_relaxed(im_in)   (minimised)
+
+    with the train-mode likelihoods at zero noise (LowerBound rules and the detached EntropyBottleneck sign included);
+    g_s is not run.  Prologue, L-inf box, the per-image branch rule, Adam and the LR table are the base class's.  The
+    backward follows RDTrainer.step's entropy path without any parameter gradient: ica_rate_gc / ica_rate_eb give the
+    value gradients, the packed .bwd convs carry them through h_s and h_a.  The step is deterministic and an image's
+    gradient does not depend on its batch.  bpp_relaxed[B]: the last -loss_o of each image (NaN before its first
+    expensive step)."""
+
+    def __init__(self, kern: CodecKernels, im_s: torch.Tensor, steps=1001, epsilon=16.0, noise_thr=1e-4, lr=0.01,
+                 att_metric="L2", clamp=True, init_noise=None, coupled=False, group=None, target=None, roi=None,
+                 pad=None, padding_mode="reflect"):
+        model = kern.model if isinstance(kern, CodecKernels) else type(kern).__name__
+        rate_attack_guard(model, getattr(kern, "precision", None), att_metric, coupled, target, roi)
+        super().__init__(kern, im_s, steps, epsilon, noise_thr, lr, "L2", clamp, init_noise, pad=pad,
+                         padding_mode=padding_mode)
+        self.rscale = float(1.0 / (math.log(2) * self.H * self.W))
+        self.bpp_relaxed = torch.full((self.B,), float("nan"), device=im_s.device)
+
+    def network_grad(self, idx=None, E=None):
+        """d loss_o / d im_in (nChw4c, C = 3) for the images idx (all when None)."""
+        kern, s = self.kern, self.rscale
+        N, M = kern.N, kern.M
+        Bn = self.B if idx is None else E
+        im4 = self._gather(self.im_in4, idx, Bn)
+        y4, sa = kern.g_a(im4, save=True)
+        del im4
+        if kern.model == "factorized":
+            gy, sumln = K.rate_eb(y4, M, kern.eb, s)
+        else:
+            ha, hs = kern.ha.convs, kern.hs.convs
+            a4 = K.abs_(y4)
+            z1, _, _ = K.conv_down(a4, M, ha[0].fwd, ha[0].bias, N, 3, 1, K.EPI_RELU)
+            z2, _, _ = K.conv_down(z1, N, ha[1].fwd, ha[1].bias, N, 5, 2, K.EPI_RELU)
+            z4, _, _ = K.conv_down(z2, N, ha[2].fwd, ha[2].bias, N, 5, 2, K.EPI_BIAS)
+            del a4
+            gz_eb, zsum = K.rate_eb(z4, N, kern.eb, s)
+            s1, _, _ = K.conv_up(z4, N, hs[0].fwd, hs[0].bias, N, K.EPI_RELU)   # the unrounded z
+            s2, _, _ = K.conv_up(s1, N, hs[1].fwd, hs[1].bias, N, K.EPI_RELU)
+            sig4, _, _ = K.conv_down(s2, N, hs[2].fwd, hs[2].bias, M, 3, 1, K.EPI_RELU)
+            gy, g, ysum = K.rate_gc(y4, M, sig4, s)   # g: through h_s's final ReLU already
+            del sig4
+            # h_s backward
+            g, _, _ = K.conv_down(g, M, hs[2].bwd, None, N, 3, 1, K.EPI_BIAS)
+            K.relu_bwd_(g, s2)
+            g, _, _ = K.conv_down(g, N, hs[1].bwd, None, N, 5, 2, K.EPI_BIAS)
+            K.relu_bwd_(g, s1)
+            gz, _, _ = K.conv_down(g, N, hs[0].bwd, None, N, 5, 2, K.EPI_BIAS)
+            gz.add_(gz_eb)
+            # h_a backward
+            g, _, _ = K.conv_up(gz, N, ha[2].bwd, None, N, K.EPI_BIAS)
+            K.relu_bwd_(g, z2)
+            g, _, _ = K.conv_up(g, N, ha[1].bwd, None, N, K.EPI_BIAS)
+            K.relu_bwd_(g, z1)
+            g, _, _ = K.conv_down(g, N, ha[0].bwd, None, M, 3, 1, K.EPI_BIAS)
+            gy.add_(K.abs_bwd_(g, y4))
+            sumln = ysum + zsum
+        relaxed = sumln * (-s)
+        if idx is None:   # a speculated whole-batch step may hold cheap images: theirs stay
+            self.bpp_relaxed = torch.where(self.loss_i > self.thr, self.bpp_relaxed, relaxed)
+        else:
+            self.bpp_relaxed.index_copy_(0, idx.long(), relaxed)
+        return kern.g_a_backward(gy, sa)
+
+
+def rate_attack_batch(kern: CodecKernels, im_s, steps=1001, epsilon=16.0, noise_thr=1e-4, lr=0.01, clamp=True,
+                      init_noise=None, eval_msssim=True, record=False, pad=None,
+                      padding_mode="reflect") -> AttackResult:
+    """attack_batch with the bitrate objective (RateAttackLoop).  bpp_ori / bpp are the true eval-mode numbers
+    (rounded latents) of eval_forward / evaluate, as for the distortion attack."""
+    loop = RateAttackLoop(kern, im_s, steps, epsilon, noise_thr, lr, "L2", clamp, init_noise, pad=pad,
+                          padding_mode=padding_mode)
+    branches = loop.run(record=record)
+    im_, out, bpp, mse_in, mse_out, msim_in, msim_out, vi, vi_msim = evaluate(
+        kern, loop.im_in, loop.im_s, loop.output_s, clamp, adv=False, msssim=eval_msssim)
+    return AttackResult(im_adv=im_, output_adv=out, output_s=loop.output_s, bpp_ori=loop.bpp_ori, bpp=bpp,
+                        mse_in=mse_in, mse_out=mse_out, msim_in=msim_in, msim_out=msim_out, vi=vi, vi_msim=vi_msim,
+                        noise=loop.noise, branches=branches)
 
 
 def ifgsm_batch(kern: CodecKernels, im_s, steps=10, epsilon=16.0, momentum=False, clamp=True, x0=None):

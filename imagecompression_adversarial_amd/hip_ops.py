@@ -664,6 +664,40 @@ def bits_to_bpp(sumlog: torch.Tensor, num_pixels: int) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------- #
+# Bitrate attack: value gradients of the entropy models (ica_rate.hip)
+# --------------------------------------------------------------------------- #
+def _check_latent(x4, C, name):
+    _dev_check(x4, name)
+    if x4.dim() != 5 or x4.shape[4] != 4 or x4.shape[1] != c4(C):
+        raise ValueError(f"{name} {tuple(x4.shape)} is not an nChw4c tensor of {C} channels")
+    return x4.shape[0], x4.shape[2], x4.shape[3]
+
+
+def rate_gc(y4: torch.Tensor, C: int, sigma4: torch.Tensor, scale: float):
+    """L = scale * sum ln lik of the zero-noise train-mode GaussianConditional on the unrounded y (scale > 0):
+    (dL/dy, dL/dsigma with h_s's final ReLU backward folded in, per-image sum ln lik [B])."""
+    N, H, W = _check_latent(y4, C, "y4")
+    if _check_latent(sigma4, C, "sigma4") != (N, H, W):
+        raise ValueError("rate_gc: y4 and sigma4 shapes differ")
+    gy, gs = torch.empty_like(y4), torch.empty_like(y4)
+    part = torch.empty(N * int(lib().ica_rate_gc_blocks()), device=y4.device)
+    call("ica_rate_gc", ptr(y4), ptr(sigma4), ptr(gy), ptr(gs), ptr(part), N, C, H, W, float(scale), stream())
+    return gy, gs, reduce_rows(part, N)
+
+
+def rate_eb(v4: torch.Tensor, C: int, eb: PackedEB, scale: float):
+    """L = scale * sum ln lik of the zero-noise train-mode EntropyBottleneck on the unrounded v (scale > 0):
+    (dL/dv, per-image sum ln lik [B]).  No parameter gradient."""
+    N, H, W = _check_latent(v4, C, "v4")
+    if eb.C != C:
+        raise ValueError(f"rate_eb: the bottleneck has {eb.C} channels, the tensor {C}")
+    gv = torch.empty_like(v4)
+    part = torch.empty(N * int(lib().ica_rate_eb_blocks(C, H, W)), device=v4.device)
+    call("ica_rate_eb", ptr(v4), ptr(eb.prm), ptr(gv), ptr(part), N, C, H, W, float(scale), stream())
+    return gv, reduce_rows(part, N)
+
+
+# --------------------------------------------------------------------------- #
 # Training-side wrappers (ica_train.hip)
 # --------------------------------------------------------------------------- #
 def wgrad(Sm4, A, Lg4, Bc, KS, S, out, accumulate=False, tag=None):

@@ -421,6 +421,29 @@ int ica_latent_distrib(const float* y4, const float* scales4, const float* means
                        int H, int W, float vmin, int nbins, float scale_floor, float pred_floor, int* hist,
                        float* pred, float* bits, float* work, hipStream_t stream);
 
+/* ---- bitrate attack: entropy-model value gradients (ica_rate.hip) -----------
+ * The expensive branch of attack_rd -r minimises  L = scale * sum ln lik  (scale = 1 / (ln 2 * H_img * W_img) > 0,
+ * so L = -bpp of the relaxed codec): the train-mode likelihoods of the UNROUNDED latents with zero noise
+ * (CompressAI GaussianConditional / EntropyBottleneck, likelihood LowerBound 1e-9, scale LowerBound 0.11, the
+ * detached EntropyBottleneck sign).  Both launches read fp32 nChw4c tensors [B][ceil(C/4)][H][W][4] (16-byte
+ * aligned), write the gradient with respect to the values only (padding lanes c >= C: 0) and per-block partial sums
+ * of ln lik; ica_reduce_rows(part, sumln, B, blocks, 1) gives sum ln lik per image.  Fixed-order sums, no float
+ * atomics: an image's numbers are the same bits alone and in a batch.  Status: 0; -5 for a non-positive or oversized
+ * shape (B or ceil(C/4) > 65535, H * W > 2^28 - 1, >= 2^47 elements), scale not in (0, inf), a missing or misaligned
+ * pointer; -7 for an output that overlaps an input or the other output.  Nothing is launched then.
+ *
+ * ica_rate_gc: lik = max(Phi((.5 - |y|) / s) - Phi((-.5 - |y|) / s), 1e-9), s = max(sigma, 0.11).  gy = dL/dy,
+ * gsig = dL/dsigma with the scale bound's pass-through rule and the backward of the ReLU that produced sigma folded
+ * in (sigma <= 0: 0).  part: B * ica_rate_gc_blocks() floats.
+ * ica_rate_eb: lik = max(|sigmoid(sg F(v + .5)) - sigmoid(sg F(v - .5))|, 1e-9) with prm[C][58] of ica_pack_eb.
+ * gv = dL/dv.  part: B * ica_rate_eb_blocks(C, H, W) floats. */
+int ica_rate_gc_blocks(void);
+int ica_rate_eb_blocks(int C, int H, int W);
+int ica_rate_gc(const float* y4, const float* sigma4, float* gy4, float* gsig4, float* part, int B, int C, int H,
+                int W, float scale, hipStream_t stream);
+int ica_rate_eb(const float* v4, const float* prm, float* gv4, float* part, int B, int C, int H, int W, float scale,
+                hipStream_t stream);
+
 /* ---- patch-wise VI localisation (ica_patch.hip) ----------------------------
  * psnr_partial (attack_patch.py:119-146) on four planar NCHW fp32 tensors [B][3][H][W], per image.  With
  * nh = (H - win) / stride + 1 and nw likewise: mse_in / mse_out [B][nh][nw] are the means over the 3 * win^2 window
