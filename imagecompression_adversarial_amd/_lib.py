@@ -96,6 +96,9 @@ _SIGS = {
     "ica_rate_eb_blocks": [_i, _i, _i],
     "ica_rate_gc": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
     "ica_rate_eb": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
+    # RD evaluation: the loss side of batch_test (ica_rdeval.hip)
+    "ica_rd_metrics_blocks": [],
+    "ica_rd_metrics": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     # patch-wise VI localisation (ica_patch.hip)
     "ica_patch_vi_ws_size": [_i, _i, _i, _i, _i],
     "ica_patch_vi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],

@@ -444,6 +444,23 @@ int ica_rate_gc(const float* y4, const float* sigma4, float* gy4, float* gsig4, 
 int ica_rate_eb(const float* v4, const float* prm, float* gv4, float* part, int B, int C, int H, int W, float scale,
                 hipStream_t stream);
 
+/* ---- RD evaluation: the loss side of batch_test (ica_rdeval.hip) -------------
+ * RateDistortionLoss(training=False) (train.py:50-70) on what the eval forward left on the device, per image, in one
+ * launch: xhat4 fp32 nChw4c [B][1][H][W][4], target NCHW [B][3][H][W], liky4 [B][ceil(Cy/4)][Hy][Wy][4] and the
+ * optional likz4 likewise (NULL with Cz = Hz = Wz = 0 for the factorized model).  out [B][3][H][W] receives
+ * clamp(x_hat, 0, 1); part (3 * B * ica_rd_metrics_blocks() floats) the per-block partials [B][3][blocks] of
+ * sse = sum (clamp(x_hat) - target)^2, lny = sum ln max(lik_y, 2^-16) and lnz (0 without z):
+ * ica_reduce_rows(part, sums, 3 * B, blocks, 1) gives sums[B][3].  nclamp [B] (int32, zeroed by the call) counts the
+ * likelihood elements below 2^-16.  Padding lanes (c >= C) add nothing.  Fixed-order sums, no float atomics: an
+ * image's numbers are the same bits alone and in a batch; the census uses integer atomics.  Status: 0; -5 for a
+ * non-positive or oversized shape (B or ceil(C/4) > 65535, H * W > 2^28 - 1, >= 2^47 elements), a z shape without a
+ * z plane, a missing required pointer or a misaligned nChw4c pointer; -7 for an output that overlaps an input.
+ * Nothing is launched then. */
+int ica_rd_metrics_blocks(void);
+int ica_rd_metrics(const float* xhat4, const float* target, const float* liky4, const float* likz4, float* out,
+                   float* part, int* nclamp, int B, int H, int W, int Cy, int Hy, int Wy, int Cz, int Hz, int Wz,
+                   hipStream_t stream);
+
 /* ---- patch-wise VI localisation (ica_patch.hip) ----------------------------
  * psnr_partial (attack_patch.py:119-146) on four planar NCHW fp32 tensors [B][3][H][W], per image.  With
  * nh = (H - win) / stride + 1 and nw likewise: mse_in / mse_out [B][nh][nw] are the means over the 3 * win^2 window
