@@ -99,6 +99,7 @@ _SIGS = {
     # RD evaluation: the loss side of batch_test (ica_rdeval.hip)
     "ica_rd_metrics_blocks": [],
     "ica_rd_metrics": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "ica_val_metrics": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     # patch-wise VI localisation (ica_patch.hip)
     "ica_patch_vi_ws_size": [_i, _i, _i, _i, _i],
     "ica_patch_vi": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],

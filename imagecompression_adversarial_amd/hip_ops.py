@@ -700,47 +700,74 @@ def rate_eb(v4: torch.Tensor, C: int, eb: PackedEB, scale: float):
 # --------------------------------------------------------------------------- #
 # RD evaluation: the loss side of batch_test (ica_rdeval.hip)
 # --------------------------------------------------------------------------- #
+def _rd_check(fn, x_hat4, target, lik_y4, Cy, lik_z4, Cz):
+    """The tensor checks rd_metrics and val_metrics share: (B, H, W, y shape, z shape), or a ValueError."""
+    for t, nm in ((x_hat4, "x_hat4"), (target, "target"), (lik_y4, "lik_y4"), (lik_z4, "lik_z4")):
+        if t is None and nm != "lik_z4":
+            raise ValueError(f"{fn}: {nm} is missing")
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32
+                              or not t.is_contiguous()):
+            raise ValueError(f"{fn}: {nm} must be a contiguous float32 HIP tensor")
+    B, H, W = check_image(target, "target")
+    if x_hat4.dim() != 5 or tuple(x_hat4.shape) != (B, 1, H, W, 4):
+        raise ValueError(f"{fn}: x_hat4 {tuple(x_hat4.shape)} is not the nChw4c reconstruction of target "
+                         f"{tuple(target.shape)}")
+    shapes = []
+    for t, C, nm in ((lik_y4, Cy, "lik_y4"), (lik_z4, Cz, "lik_z4")):
+        if t is None:
+            if C:
+                raise ValueError(f"{fn}: {C} z channels without a z plane")
+            shapes.append((0, 0, 0))
+            continue
+        if not isinstance(C, int) or C < 1 or t.dim() != 5 or t.shape[4] != 4 or t.shape[1] != c4(C):
+            raise ValueError(f"{fn}: {nm} {tuple(t.shape)} is not an nChw4c tensor of {C} channels")
+        if t.shape[0] != B:
+            raise ValueError(f"{fn}: {nm} holds {t.shape[0]} images, target {B}")
+        shapes.append((C, t.shape[2], t.shape[3]))
+    return B, H, W, shapes[0], shapes[1]
+
+
+def _rd_status(fn, rc):
+    if rc in (-5, -7):
+        raise ValueError(f"{fn} refused its arguments (status {rc})")
+    if rc != 0:
+        raise RuntimeError(f"{fn} failed with status {rc}")
+
+
 def rd_metrics(x_hat4: torch.Tensor, target: torch.Tensor, lik_y4: torch.Tensor, Cy: int, lik_z4=None, Cz: int = 0):
     """RateDistortionLoss(training=False)'s sums per image, in one launch on the eval forward's tensors:
     (sse [B] = sum (clamp(x_hat, 0, 1) - target)^2, lny [B] = sum ln max(lik_y, 2^-16), lnz [B] (0 without lik_z4),
     nclamp [B] int32 = likelihood elements below 2^-16, clamp(x_hat, 0, 1) as NCHW [B, 3, H, W]).
     x_hat4: fp32 nChw4c [B, 1, H, W, 4]; target: NCHW; lik_y4 / lik_z4: nChw4c of Cy / Cz channels.  Anything else
     is a ValueError and launches nothing."""
-    for t, nm in ((x_hat4, "x_hat4"), (target, "target"), (lik_y4, "lik_y4"), (lik_z4, "lik_z4")):
-        if t is None and nm != "lik_z4":
-            raise ValueError(f"rd_metrics: {nm} is missing")
-        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32
-                              or not t.is_contiguous()):
-            raise ValueError(f"rd_metrics: {nm} must be a contiguous float32 HIP tensor")
-    B, H, W = check_image(target, "target")
-    if x_hat4.dim() != 5 or tuple(x_hat4.shape) != (B, 1, H, W, 4):
-        raise ValueError(f"rd_metrics: x_hat4 {tuple(x_hat4.shape)} is not the nChw4c reconstruction of target "
-                         f"{tuple(target.shape)}")
-    shapes = []
-    for t, C, nm in ((lik_y4, Cy, "lik_y4"), (lik_z4, Cz, "lik_z4")):
-        if t is None:
-            if C:
-                raise ValueError(f"rd_metrics: {C} z channels without a z plane")
-            shapes.append((0, 0, 0))
-            continue
-        if not isinstance(C, int) or C < 1 or t.dim() != 5 or t.shape[4] != 4 or t.shape[1] != c4(C):
-            raise ValueError(f"rd_metrics: {nm} {tuple(t.shape)} is not an nChw4c tensor of {C} channels")
-        if t.shape[0] != B:
-            raise ValueError(f"rd_metrics: {nm} holds {t.shape[0]} images, target {B}")
-        shapes.append((C, t.shape[2], t.shape[3]))
+    B, H, W, ys, zs = _rd_check("rd_metrics", x_hat4, target, lik_y4, Cy, lik_z4, Cz)
     nblk = int(lib().ica_rd_metrics_blocks())
     dev = target.device
     out = torch.empty_like(target)
     part = torch.empty(B * 3 * nblk, device=dev)
     nclamp = torch.empty(B, dtype=torch.int32, device=dev)
     rc = lib().ica_rd_metrics(ptr(x_hat4), ptr(target), ptr(lik_y4), ptr(lik_z4), ptr(out), ptr(part), ptr(nclamp),
-                              B, H, W, *shapes[0], *shapes[1], stream())
-    if rc in (-5, -7):
-        raise ValueError(f"ica_rd_metrics refused its arguments (status {rc})")
-    if rc != 0:
-        raise RuntimeError(f"ica_rd_metrics failed with status {rc}")
+                              B, H, W, *ys, *zs, stream())
+    _rd_status("ica_rd_metrics", rc)
     sums = reduce_rows(part, 3 * B).view(B, 3)
     return sums[:, 0], sums[:, 1], sums[:, 2], nclamp, out
+
+
+def val_metrics(x_hat4: torch.Tensor, target: torch.Tensor, lik_y4: torch.Tensor, Cy: int, lik_z4=None, Cz: int = 0,
+                want_x_hat: bool = False):
+    """RateDistortionLoss(training=True)'s sums per image on an EVAL forward's tensors (the trainer's validation), in
+    one launch: (sse [B] = sum (x_hat - target)^2 of the unclamped reconstruction, lny [B] = sum ln max(lik_y, 2^-16),
+    lnz [B] (0 without lik_z4), the unclamped x_hat as NCHW [B, 3, H, W] when want_x_hat, else None).  Arguments and
+    errors as rd_metrics."""
+    B, H, W, ys, zs = _rd_check("val_metrics", x_hat4, target, lik_y4, Cy, lik_z4, Cz)
+    nblk = int(lib().ica_rd_metrics_blocks())
+    out = torch.empty_like(target) if want_x_hat else None
+    part = torch.empty(B * 3 * nblk, device=target.device)
+    rc = lib().ica_val_metrics(ptr(x_hat4), ptr(target), ptr(lik_y4), ptr(lik_z4), ptr(out), ptr(part),
+                               B, H, W, *ys, *zs, stream())
+    _rd_status("ica_val_metrics", rc)
+    sums = reduce_rows(part, 3 * B).view(B, 3)
+    return sums[:, 0], sums[:, 1], sums[:, 2], out
 
 
 # --------------------------------------------------------------------------- #

@@ -460,6 +460,14 @@ int ica_rd_metrics_blocks(void);
 int ica_rd_metrics(const float* xhat4, const float* target, const float* liky4, const float* likz4, float* out,
                    float* part, int* nclamp, int B, int H, int W, int Cy, int Hy, int Wy, int Cz, int Hz, int Wz,
                    hipStream_t stream);
+/* ica_val_metrics: the trainer's validation (validate.py; the reference's test_epoch scores an eval forward with
+ * RateDistortionLoss(training=True), train.py:217-229).  The same tensors, partials and status codes as
+ * ica_rd_metrics, with three differences: sse = sum (x_hat - target)^2 of the UNCLAMPED reconstruction; out receives
+ * the unclamped x_hat as NCHW and may be NULL, which skips the store (only the ms-ssim metric reads it); there is no
+ * census.  part: 3 * B * ica_rd_metrics_blocks() floats, reduced by ica_reduce_rows as above. */
+int ica_val_metrics(const float* xhat4, const float* target, const float* liky4, const float* likz4, float* out,
+                    float* part, int B, int H, int W, int Cy, int Hy, int Wy, int Cz, int Hz, int Wz,
+                    hipStream_t stream);
 
 /* ---- patch-wise VI localisation (ica_patch.hip) ----------------------------
  * psnr_partial (attack_patch.py:119-146) on four planar NCHW fp32 tensors [B][3][H][W], per image.  With
