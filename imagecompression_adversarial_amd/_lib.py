@@ -33,21 +33,17 @@ _SIGS = {
     "ica_pack_conv_weight_x6_size": [_i, _i, _i, _i],
     "ica_pack_gdn_x6": [_p, _p, _i, _p],
     "ica_pack_gdn_x6_size": [_i],
-    "ica_pack_up3_bf16": [_p, _p, _i, _p],
-    "ica_pack_up3_x6": [_p, _p, _i, _p],
     "ica_pack_up3k3_x6_size": [_i],
     "ica_pack_up3k3_x6": [_p, _p, _p, _i, _p],
     "ica_conv_up3k3_x6": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "ica_conv_up3_x6": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "ica_conv_up3_bf16": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ica_conv_ex": [_p, _p],
     "ica_last_launch": [_p, _i, _p],
     "ica_x6_tiling": [_i],
     "ica_pack_gdn": [_p, _p, _p, _p, _i, _i, _f, _p],
     "ica_pack_gdn_bf16": [_p, _p, _p, _p, _i, _i, _f, _p],
     "ica_pack_up3_size": [_i],
-    "ica_pack_up3": [_p, _p, _i, _p],
-    "ica_conv_up3": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "ica_pack_up3": [_p, _p, _i, _i, _p],
+    "ica_conv_up3": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     "ica_elem_blocks_per_image": [],
     "ica_nchw_to_nc4": [_p, _p, _i, _i, _i, _i, _p],
     "ica_nc4_to_nchw": [_p, _p, _i, _i, _i, _i, _p],

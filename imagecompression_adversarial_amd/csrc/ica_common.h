@@ -177,8 +177,22 @@ inline const void* ica_fnptr(F* f) {   // a kernel (function designator or point
     hipLaunchKernelGGL(kern, ica_g_, ica_b_, lds, st, __VA_ARGS__);                                          \
   } while (0)
 
+// ICA_LAUNCH for a kernel that needs more dynamic LDS than the 64 KB default: the first launch from each site (one
+// per kernel instantiation: the launchers are templates over their kernel's parameters) raises the kernel's ceiling
+// to the CU's whole LDS; the launch itself takes the caller's `lds` bytes and is recorded as by ICA_LAUNCH.
+constexpr int ICA_CU_LDS_BYTES = 160 * 1024;
+#define ICA_LAUNCH_LDS(kern, grid, block, lds, st, ...)                                                           \
+  do {                                                                                                           \
+    static bool ica_attr_set_ = false;                                                                           \
+    if (!ica_attr_set_) {                                                                                        \
+      (void)hipFuncSetAttribute(ica_fnptr(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ICA_CU_LDS_BYTES);  \
+      ica_attr_set_ = true;                                                                                      \
+    }                                                                                                            \
+    ICA_LAUNCH(kern, grid, block, lds, st, __VA_ARGS__);                                                         \
+  } while (0)
+
 // In-kernel clock (diagnostic builds only, -DICA_CLOCK_STAMP via scripts/build_variant.sh; the product library
-// compiles these to nothing).  Wave 0 of each block stamps the shader clock (s_memtime) and the 100 MHz real-time
+// compiles these to nothing; it is the only build flag the sources know).  Wave 0 of each block stamps the shader clock (s_memtime) and the 100 MHz real-time
 // counter at kernel entry (record words 0, 1) and exit (words 6, 7), and optionally the shader clock at phase
 // boundaries (ICA_STAMP_AT(k), words 2..5) and per wave (ICA_STAMP_WAVE, words 8..15), into a buffer of its own
 // (ica_diag_stamp_buffer): 16 words per block,

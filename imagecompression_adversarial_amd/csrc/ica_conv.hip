@@ -61,14 +61,6 @@ ICA_DEV void load_frag(float (&a)[IT][KH], const float* w) {
 // L1 -> register stream of 4 KB per wave-step, the bf16 main loop's limit) feeds twice the MFMAs
 template <int CC, bool BF>
 constexpr int down_pt() { return (BF && CC == 16) ? 2 : 1; }
-// the x6 k3 conv_down at two rows per wave on large grids (ICA_X6O_PT2=0 builds: one row; ICA_X6O_PT2_GDN=0: one row
-// for the GDN / IGDN (backward) epilogues -- for A/B runs)
-#ifndef ICA_X6O_PT2
-#define ICA_X6O_PT2 1
-#endif
-#ifndef ICA_X6O_PT2_GDN
-#define ICA_X6O_PT2_GDN 1
-#endif
 
 // occupancy target: 2 blocks/CU, except the k5 IT = 6 (C = 192, bmshj2018 q6-8) variants, whose 6-tile
 // accumulators + fragment ring + GDN epilogue need the whole 512-register file (1 block/CU, no spills)
@@ -93,7 +85,7 @@ constexpr int conv_down_waves() {
 template <int KS, int S, int IT, int CC, int TW, int EPI, int FX, bool BF, bool X6O = false, int XPT = 1, int NPL = 3>
 __global__ __launch_bounds__(256, X6O ? (IT == 1 ? 2 : 1) : (conv_down_waves<KS, IT, CC, EPI, BF>())) void conv_down_kernel(ConvParams p) {
   constexpr int PT = X6O ? XPT : down_pt<CC, BF>();
-  static_assert(XPT == 1 || (X6O && XPT == 2 && (ICA_X6O_PT2_GDN || !epi_gdn<EPI>()) && IT >= 4), "x6 conv_down: two rows per wave at IT >= 4");
+  static_assert(XPT == 1 || (X6O && XPT == 2 && IT >= 4), "x6 conv_down: two rows per wave at IT >= 4");
   constexpr int TH = PT * 128 / TW;
   constexpr int PR = S * (TH - 1) + KS, PC = S * (TW - 1) + KS;
   constexpr int NQ = CC / 4, KH = CC / 2, PLANE = PR * PC, PAD = KS / 2;
@@ -819,14 +811,9 @@ __global__ __launch_bounds__(256, 2) void conv_down_split_kernel(ConvParams p) {
 // bf16 path doubles the rows: each wave then runs two 32-pixel tiles per class (up_pt), so a weight
 // fragment feeds twice the MFMAs (as in conv_down).
 constexpr int UP_TW = 16, UP_PC = UP_TW + 2;
-#ifndef ICA_BF_UP3_OLD
-#define ICA_BF_UP3_OLD 0   // A/B builds: 1 = the bf16 Z-gather on conv_up3_kernel<true> (rounds 1-5)
-#endif
-#ifndef ICA_BF_UP_PT
-#define ICA_BF_UP_PT 2   // A/B builds: pixel tiles per wave and class of the bf16 conv_up (4: one block per CU)
-#endif
+constexpr int BF_UP_PT = 2;   // pixel tiles per wave and class of the bf16 conv_up
 template <bool BF>
-constexpr int up_pt() { return BF ? ICA_BF_UP_PT : 1; }
+constexpr int up_pt() { return BF ? BF_UP_PT : 1; }
 template <bool BF>
 constexpr int up_th() { return 4 * up_pt<BF>(); }
 template <bool BF>
@@ -964,11 +951,8 @@ ICA_DEV void conv_up_acc(const ConvParams& p, const f32x4* patch, int jt, int cb
   }
 }
 
-// the bf16 GDN-backward epilogue's (y, s) loads (conv_epilogue EAG): a two-channel-tile ring (ICA_UP_EAG=0 builds:
-// beside their use, the round-4 form, for A/B runs)
-#ifndef ICA_UP_EAG
-#define ICA_UP_EAG 2
-#endif
+// the bf16 GDN-backward epilogue's (y, s) loads (conv_epilogue EAG): a two-channel-tile ring
+constexpr int UP_EAG = 2;
 // the epilogue of class (PY, PX) for the pixel tiles of row group jt
 template <int PY, int PX, int IT, int EPI, int FX, bool BF>
 ICA_DEV void conv_up_store(const ConvParams& p, f32x16 (&acc)[up_pt<BF>()][IT], int n, int a0, int b0, int jt,
@@ -979,8 +963,8 @@ ICA_DEV void conv_up_store(const ConvParams& p, f32x16 (&acc)[up_pt<BF>()][IT], 
 #pragma unroll
   for (int t = 0; t < PT; ++t) {
     const int oy = 2 * (a0 + a_rel + 2 * t) + PY, ox = 2 * (b0 + b_rel) + PX;
-    conv_epilogue<IT, EPI, FX, BF, 0, up_lg<IT, BF>(), ICA_UP_EAG>(p, acc[t], n, oy, ox, oy < p.Hout && ox < p.Wout,
-                                                               cb * IT * 32, lp);
+    conv_epilogue<IT, EPI, FX, BF, 0, up_lg<IT, BF>(), UP_EAG>(p, acc[t], n, oy, ox, oy < p.Hout && ox < p.Wout,
+                                                           cb * IT * 32, lp);
   }
 }
 
@@ -1022,7 +1006,7 @@ ICA_DEV void conv_up_pair(const ConvParams& p, const f32x4* patch, int n, int a0
 }
 
 template <int KS, int IT, int EPI, int FX, bool BF>
-__global__ __launch_bounds__(256, ((BF && ICA_BF_UP_PT > 2) ? 1 : conv_min_blocks<KS, IT>())) void conv_up_kernel(ConvParams p) {
+__global__ __launch_bounds__(256, (conv_min_blocks<KS, IT>())) void conv_up_kernel(ConvParams p) {
   ICA_STAMP_BEGIN();
   extern __shared__ f32x4 patch[];  // fp32: [Cin/4][TH+2][UP_PC] f32x4; bf16: [Cin/8][TH+2][UP_PC] bf16x8
   constexpr int UP_TH = up_th<BF>(), UP_PLANE = up_plane<BF>();
@@ -1447,7 +1431,7 @@ template <int CT>
 constexpr int u3_npx() { return 4 * CT * U3_HW; }
 
 // BF: the same persistent pipeline on bf16 operands (config 5's g_s.6 forward / g_a.0 input gradient; bf16 nChw4c
-// activations, 8-B channel quads; the ica_pack_up3_bf16 fragments, one plane): one MFMA per chunk and row tile, no
+// activations, 8-B channel quads; the ica_pack_up3 prec-1 fragments, one plane): one MFMA per chunk and row tile, no
 // split.  It replaced conv_up3_kernel<true> (one block of 5 x 32 input pixels, loads up front, 1.2 ms per launch at
 // the config-5 shapes).
 template <int NCH, int CT, bool BF = false>
@@ -1814,7 +1798,7 @@ static int pick_tw_down_x6o(const ConvParams& p, hipStream_t st) {
     // two rows per wave (half the weight-fragment stream per MFMA) where the halved grid still gives every CU
     // >= 4 blocks (k3 lrelu 9.66 -> 8.56 ms, gdn+res 12.05 -> 10.81 ms, gdn_bwd 12.2 -> 10.9 ms at the config-3
     // shapes; the GDN epilogues run tile by tile, the second tile's accumulators held)
-    if constexpr (ICA_X6O_PT2 && (ICA_X6O_PT2_GDN || !epi_gdn<EPI>()) && IT >= 4) {
+    if constexpr (IT >= 4) {
       const int cbs = (p.Cout + IT * 32 - 1) / (IT * 32);
       if (p.Wout >= 32 && p.Wout % 32 == 0) {
         if ((long)(p.Wout / 32) * ((p.Hout + 7) / 8) * p.N * cbs >= 1024)
@@ -2003,14 +1987,8 @@ static int launch_up_small(const ConvParams& p, hipStream_t st) {
   const int tiles = ((p.Win + UP_TW - 1) / UP_TW) * ((p.Hin + UPS_TH - 1) / UPS_TH) * p.N;
   dim3 grid(4 * tiles, (p.Cout + IT * 32 - 1) / (IT * 32));
   const size_t lds = (size_t)std::max((p.Cin / 4) * UPS_PLANE, ups_red_entries<IT>()) * sizeof(f32x4);
-  if (lds > 160 * 1024) return -2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up_small_kernel<KS, IT, EPI, FX>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  ICA_LAUNCH((conv_up_small_kernel<KS, IT, EPI, FX>), grid, dim3(256), lds, st, p);
+  if (lds > ICA_CU_LDS_BYTES) return -2;
+  ICA_LAUNCH_LDS((conv_up_small_kernel<KS, IT, EPI, FX>), grid, dim3(256), lds, st, p);
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2028,14 +2006,8 @@ static int launch_up(const ConvParams& p, hipStream_t st) {
   dim3 grid(tiles, (p.Cout + IT * 32 - 1) / (IT * 32));
   const size_t lds = ((size_t)(p.Cin / (BF ? 8 : 4)) * up_plane<BF>() +
                       (up_lg<IT, BF>() ? epi_lds_entries<IT, EPI>() : 0)) * sizeof(f32x4);
-  if (lds > 160 * 1024) return -2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up_kernel<KS, IT, EPI, FX, BF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  ICA_LAUNCH((conv_up_kernel<KS, IT, EPI, FX, BF>), grid, dim3(256), lds, st, p);
+  if (lds > ICA_CU_LDS_BYTES) return -2;
+  ICA_LAUNCH_LDS((conv_up_kernel<KS, IT, EPI, FX, BF>), grid, dim3(256), lds, st, p);
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2260,10 +2232,20 @@ size_t ica_pack_up3_size(int Cin) { return (size_t)3 * (Cin / 16) * 64 * 8; }
 
 // w: transposed-conv weight view [Cin][3][5][5] contiguous (ConvTranspose2d(Cin,3) weight,
 // or Conv2d(3,Cin) weight [Cin_out=Cin][3][5][5] used for its input-gradient).
-int ica_pack_up3(const float* w, float* dst, int Cin, hipStream_t st) {
+// dst by prec: 0 = ica_pack_up3_size(Cin) fp32 fragments; 1 = the same fragments rounded to bf16; 2 = three bf16
+// planes of the fp32 fragment order (3 * ica_pack_up3_size(Cin) values).
+int ica_pack_up3(const float* w, void* dst, int Cin, int prec, hipStream_t st) {
   if (Cin % 16 != 0) return -2;
+  if (prec < 0 || prec > 2) return -4;
   const long total = (long)ica_pack_up3_size(Cin);
-  ICA_LAUNCH(pack_up3_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, st, w, dst, Cin, total);
+  const dim3 grid((total + 255) / 256), block(256);
+  if (prec == 0) {
+    ICA_LAUNCH(pack_up3_kernel<float>, grid, block, 0, st, w, reinterpret_cast<float*>(dst), Cin, total);
+  } else if (prec == 1) {
+    ICA_LAUNCH(pack_up3_kernel<__bf16>, grid, block, 0, st, w, reinterpret_cast<__bf16*>(dst), Cin, total);
+  } else {
+    ICA_LAUNCH(pack_up3_x6_kernel, grid, block, 0, st, w, reinterpret_cast<__bf16*>(dst), Cin, total);
+  }
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2275,80 +2257,36 @@ static int up3_layout_ok(int layout, int Hin, int Win) {
   return 0;
 }
 
-int ica_conv_up3(const float* x, float* y, const float* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                 int layout, hipStream_t st) {
+// prec (as ica_conv_args.prec) names wp's pack and x's element type: 0 = fp32; 1 = bf16 operands (bf16 x);
+// 2 = fp32-accurate bf16x6.  Cin = 128 (and 192 on x6) run the persistent pipeline (conv_up3_x6p_kernel), any other
+// Cin the tiled conv_up3_kernel.
+int ica_conv_up3(const float* x, float* y, const void* wp, const float* bias, int N, int Cin, int Hin, int Win,
+                 int layout, int prec, hipStream_t st) {
   if (Cin % 16 != 0) return -2;
   if (const int rc = up3_layout_ok(layout, Hin, Win)) return rc;
-  ConvParams p{x, y, wp, bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, Cin, Hin, Win, 3,
-               2 * Hin, 2 * Win, nullptr};
-  p.pl = layout;
-  const int tiles = ((Win + T3_TW - 1) / T3_TW) * ((Hin + T3_TH - 1) / T3_TH) * N;
-  ICA_LAUNCH(conv_up3_kernel<false>, dim3(tiles), dim3(256), 0, st, p);
-  ICA_CHECK_LAUNCH();
-  return 0;
-}
-
-// fp32-accurate bf16x6 variants (prec = 2): three bf16 planes of the fp32 fragment order (3 * ica_pack_up3_size(Cin)
-// values)
-int ica_pack_up3_x6(const float* w, void* dst, int Cin, hipStream_t st) {
-  if (Cin % 16 != 0) return -2;
-  const long total = (long)ica_pack_up3_size(Cin);
-  ICA_LAUNCH(pack_up3_x6_kernel, dim3((total + 255) / 256), dim3(256), 0, st, w,
-                     reinterpret_cast<__bf16*>(dst), Cin, total);
-  ICA_CHECK_LAUNCH();
-  return 0;
-}
-
-int ica_conv_up3_x6(const float* x, float* y, const void* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                    int layout, hipStream_t st) {
-  if (Cin % 16 != 0) return -2;
-  if (const int rc = up3_layout_ok(layout, Hin, Win)) return rc;
+  if (prec < 0 || prec > 2) return -4;
   ConvParams p{x, y, reinterpret_cast<const float*>(wp), bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                N, Cin, Hin, Win, 3, 2 * Hin, 2 * Win, nullptr};
   p.pl = layout;
+  auto tiled = [&](auto kern) {
+    const int tiles = ((Win + T3_TW - 1) / T3_TW) * ((Hin + T3_TH - 1) / T3_TH) * N;
+    ICA_LAUNCH(kern, dim3(tiles), dim3(256), 0, st, p);
+  };
   auto persistent = [&](auto kern, int R) {   // 8 x nb blocks: nb per XCD, at most one per CU
     const int tiles = ((Win + U3_OW - 1) / U3_OW) * ((Hin + R - 1) / R) * N;
     const int nb = std::max(1, std::min((tiles + 7) / 8, ica_cu_count() / 8));
     ICA_LAUNCH(kern, dim3(8 * nb), dim3(256), 0, st, p);
   };
-  if (Cin == 128) {
-    persistent(conv_up3_x6p_kernel<8, 3>, u3_rows<3>());
-  } else if (Cin == 192) {
-    persistent(conv_up3_x6p_kernel<12, 2>, u3_rows<2>());
+  if (prec == 0) {
+    tiled(conv_up3_kernel<false>);
+  } else if (prec == 2) {
+    if (Cin == 128) persistent(conv_up3_x6p_kernel<8, 3>, u3_rows<3>());
+    else if (Cin == 192) persistent(conv_up3_x6p_kernel<12, 2>, u3_rows<2>());
+    else tiled(conv_up3_kernel<false, true>);
   } else {
-    const int tiles = ((Win + T3_TW - 1) / T3_TW) * ((Hin + T3_TH - 1) / T3_TH) * N;
-    ICA_LAUNCH((conv_up3_kernel<false, true>), dim3(tiles), dim3(256), 0, st, p);
+    if (Cin == 128) persistent(conv_up3_x6p_kernel<8, 3, true>, u3_rows<3>());
+    else tiled(conv_up3_kernel<true>);
   }
-  ICA_CHECK_LAUNCH();
-  return 0;
-}
-
-// bf16-operand variants (prec = 1): fragments in the fp32 order rounded to bf16 (ica_pack_up3_size(Cin) values)
-int ica_pack_up3_bf16(const float* w, void* dst, int Cin, hipStream_t st) {
-  if (Cin % 16 != 0) return -2;
-  const long total = (long)ica_pack_up3_size(Cin);
-  ICA_LAUNCH(pack_up3_kernel<__bf16>, dim3((total + 255) / 256), dim3(256), 0, st, w,
-                     reinterpret_cast<__bf16*>(dst), Cin, total);
-  ICA_CHECK_LAUNCH();
-  return 0;
-}
-
-int ica_conv_up3_bf16(const float* x, float* y, const void* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                      int layout, hipStream_t st) {
-  if (Cin % 16 != 0) return -2;
-  if (const int rc = up3_layout_ok(layout, Hin, Win)) return rc;
-  ConvParams p{x, y, reinterpret_cast<const float*>(wp), bias, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-               N, Cin, Hin, Win, 3, 2 * Hin, 2 * Win, nullptr};
-  p.pl = layout;
-  if (Cin == 128 && !ICA_BF_UP3_OLD) {   // the persistent pipeline (conv_up3_x6p_kernel<.., BF>)
-    const int tiles = ((Win + U3_OW - 1) / U3_OW) * ((Hin + u3_rows<3>() - 1) / u3_rows<3>()) * N;
-    const int nb = std::max(1, std::min((tiles + 7) / 8, ica_cu_count() / 8));
-    ICA_LAUNCH((conv_up3_x6p_kernel<8, 3, true>), dim3(8 * nb), dim3(256), 0, st, p);
-    ICA_CHECK_LAUNCH();
-    return 0;
-  }
-  const int tiles = ((Win + T3_TW - 1) / T3_TW) * ((Hin + T3_TH - 1) / T3_TH) * N;
-  ICA_LAUNCH(conv_up3_kernel<true>, dim3(tiles), dim3(256), 0, st, p);
   ICA_CHECK_LAUNCH();
   return 0;
 }

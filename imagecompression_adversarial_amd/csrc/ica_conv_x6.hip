@@ -585,21 +585,6 @@ __global__ __launch_bounds__(512, 1) void conv_down_x6w_kernel(ConvParams p, lon
 // Weights: [plane][ky][it][lane][e] (pack_conv_rgb5_x6_kernel, ica_pack_conv_weight_x6 order 2), plane stride ps.
 // --------------------------------------------------------------------------------------------------------------
 constexpr int RGB5_KY = 5, RGB5_IT = 4;
-#ifndef RGB5_STAGGER
-#define RGB5_STAGGER 0
-#endif
-#ifndef RGB5_PRIO
-#define RGB5_PRIO 0
-#endif
-#ifndef RGB5_W
-#define RGB5_W 0    // 1: the GDN / IGDN forward on the one-wave-per-SIMD kernel (conv_rgb5w_x6_kernel)
-#endif
-#ifndef RGB5_BJ
-#define RGB5_BJ 1   // 1: the backward epilogue's gamma'^T fragments one MFMA group ahead
-#endif
-#ifndef RGB5_AB
-#define RGB5_AB 0   // timing-only A/B builds (scripts/build_variant.sh): 1 = 1/16 of the forward stores, 2 = no GDN GEMM
-#endif
 constexpr int RGB5_W_BYTES = 3 * RGB5_KY * RGB5_IT * 64 * 16;            // 61440
 constexpr int RGB5_G_BYTES = 3 * RGB5_IT * RGB5_IT * 2048;               // 98304
 constexpr int RGB5_LDS = RGB5_W_BYTES + RGB5_G_BYTES + 2 * 128 * 4;      // + bias, beta': 160768
@@ -736,7 +721,6 @@ ICA_DEV void rgb5_epi_fwd(const ConvParams& p, const char* lds, f32x16 (&acc)[RG
         for (int e = 0; e < 4; ++e) nx[4 * g + e] = ev[e];
       }
       bf16x8 ga[2][3];
-#if RGB5_AB != 2 && RGB5_AB != 3
       ldg(ga[0], ct, 0);
 #pragma unroll
       for (int k = 0; k < 2 * IT; ++k) {
@@ -744,7 +728,6 @@ ICA_DEV void rgb5_epi_fwd(const ConvParams& p, const char* lds, f32x16 (&acc)[RG
         __builtin_amdgcn_sched_barrier(0);
         nx = mfma_x6(ga[k & 1], xs2[k >> 1][k & 1], nx);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
       if (valid) {
 #pragma unroll
@@ -758,88 +741,11 @@ ICA_DEV void rgb5_epi_fwd(const ConvParams& p, const char* lds, f32x16 (&acc)[RG
             yv[e] = acc[ct][4 * g + e] * sc;
           }
           const unsigned ss = (unsigned)(ct * 8 + 2 * g) * plane;
-#if RGB5_AB == 1
-          if (ct == 0 && g == 0) {
-            if (p.save_s) SS.st(vo, ss, sv);
-            Y.st(vo, ss, yv);
-          }
-#else
           if (p.save_s) SS.st(vo, ss, sv);
           Y.st(vo, ss, yv);
-#endif
         }
       }
     }
-  }
-}
-
-// the same epilogue at one wave per SIMD (512 registers): every normaliser tile at once (4 accumulation chains), x^2
-// split one k-step at a time (the round's 8 values feed all 4 output tiles), gamma' fragments from LDS one output
-// tile ahead; the ops of the narrow form, the MFMA order of gdn_fwd_x6_pair
-template <int EPI>
-ICA_DEV void rgb5_epi_fwd_wide(const ConvParams& p, const char* lds, f32x16 (&acc)[RGB5_IT], int n, int oy, int ox,
-                               bool valid) {
-  constexpr int IT = RGB5_IT;
-  static_assert(EPI == EPI_GDN || EPI == EPI_IGDN, "forward GDN epilogues");
-  const int lane = threadIdx.x & 63, h = lane >> 5;
-  const unsigned plane = (unsigned)p.Hout * p.Wout;
-  const size_t img = (size_t)((p.Cout + 3) >> 2) * plane;
-  const Img4 Y(p.y, img, n), SS(p.save_s, img, n);
-  const f32x4* bq = reinterpret_cast<const f32x4*>(lds + RGB5_W_BYTES + RGB5_G_BYTES);   // [32 bias][32 beta'] quads
-  const unsigned vo = h * plane + (valid ? pix_at(oy, ox, p.Hout, p.Wout, p.pl & PL_OUT) : 0u);
-  const char* gl = lds + RGB5_W_BYTES;
-  f32x16 nx[IT];
-#pragma unroll
-  for (int it = 0; it < IT; ++it)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const f32x4 bv = bq[it * 8 + 2 * g + h], ev = bq[32 + it * 8 + 2 * g + h];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc[it][4 * g + e] += bv[e];
-        nx[it][4 * g + e] = ev[e];
-      }
-    }
-  auto ldg = [&](bf16x8 (&a)[3], int ct, int k) {
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-      a[pl] = lds_frag(gl, (((ct * IT + (k >> 1)) * 2 + (k & 1)) * 1024) + pl * IT * IT * 2048 + lane * 16);
-  };
-  bf16x8 ga[2][3];
-  ldg(ga[0], 0, 0);
-#pragma unroll
-  for (int k = 0; k < 2 * IT; ++k) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = acc[k >> 1][8 * (k & 1) + j] * acc[k >> 1][8 * (k & 1) + j];
-    bf16x8 xq[3];
-    split3x8(v, xq);
-#pragma unroll
-    for (int ct = 0; ct < IT; ++ct) {
-      const int r = k * IT + ct;
-      if (r + 1 < 2 * IT * IT) ldg(ga[(r + 1) & 1], (r + 1) % IT, (r + 1) / IT);
-      __builtin_amdgcn_sched_barrier(0);
-      nx[ct] = mfma_x6(ga[r & 1], xq, nx[ct]);
-    }
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  if (valid) {
-#pragma unroll
-    for (int ct = 0; ct < IT; ++ct)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 yv, sv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float nv = nx[ct][4 * g + e];
-          const float sc = (EPI == EPI_GDN) ? __builtin_amdgcn_rsqf(nv) : __builtin_amdgcn_sqrtf(nv);
-          sv[e] = sc;
-          yv[e] = acc[ct][4 * g + e] * sc;
-        }
-        const unsigned ss = (unsigned)(ct * 8 + 2 * g) * plane;
-        if (p.save_s) SS.st(vo, ss, sv);
-        Y.st(vo, ss, yv);
-      }
   }
 }
 
@@ -880,7 +786,6 @@ ICA_DEV void rgb5_epi_bwd(const ConvParams& p, const char* lds, f32x16 (&acc)[RG
 #pragma unroll
   for (int jt = 0; jt < IT; ++jt) ux[jt] = f32x16{0};
   __builtin_amdgcn_sched_barrier(0);
-#if RGB5_BJ
   // fragments one MFMA group (k, jt) ahead: 24 registers instead of two rounds' 96
   bf16x8 ga[2][3];
   auto ldg = [&](bf16x8 (&a)[3], int r) {
@@ -897,24 +802,6 @@ ICA_DEV void rgb5_epi_bwd(const ConvParams& p, const char* lds, f32x16 (&acc)[RG
     const int k = r / IT, jt = r % IT;
     ux[jt] = mfma_x6(ga[r & 1], tq[k >> 1][k & 1], ux[jt]);
   }
-#else
-  bf16x8 ga[2][IT][3];
-  auto ldg = [&](bf16x8 (&a)[IT][3], int k) {
-#pragma unroll
-    for (int jt = 0; jt < IT; ++jt)
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-        a[jt][pl] = lds_frag(gl, (((jt * IT + (k >> 1)) * 2 + (k & 1)) * 1024) + pl * IT * IT * 2048 + lane * 16);
-  };
-  ldg(ga[0], 0);
-#pragma unroll
-  for (int k = 0; k < 2 * IT; ++k) {
-    if (k + 1 < 2 * IT) ldg(ga[(k + 1) & 1], k + 1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int jt = 0; jt < IT; ++jt) ux[jt] = mfma_x6(ga[k & 1][jt], tq[k >> 1][k & 1], ux[jt]);
-  }
-#endif
   if (valid) {
 #pragma unroll
     for (int jt = 0; jt < IT; ++jt)
@@ -939,17 +826,6 @@ __global__ __launch_bounds__(512, 1) void conv_rgb5_x6_kernel(ConvParams p, long
   int b, cb;
   xcd_block<true>(b, cb);
   const int t_end = min(total, b * per + per), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#if RGB5_STAGGER > 0
-  // the SIMD partners (waves w, w + 4) run the same tile program and would stay in lockstep, both in their MFMA
-  // phase, then both in their store phase; waves 4-7 start RGB5_STAGGER x 4096 cycles late
-  if (wave >= 4) {
-#pragma unroll 1
-    for (int i = 0; i < RGB5_STAGGER; ++i) __builtin_amdgcn_s_sleep(64);
-  }
-#endif
-#if RGB5_PRIO
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll 1
   for (int t = b * per + wave; t < t_end; t += 8) {
     const int tx = t % tiles_x, r = t / tiles_x;
@@ -960,57 +836,8 @@ __global__ __launch_bounds__(512, 1) void conv_rgb5_x6_kernel(ConvParams p, long
     f32x16 acc[RGB5_IT];
 #pragma unroll
     for (int it = 0; it < RGB5_IT; ++it) acc[it] = f32x16{0};
-#if RGB5_AB == 3
-#pragma unroll
-    for (int it = 0; it < RGB5_IT; ++it) acc[it] = f32x16{q[it][0][0] + q[4][1][1]};
-#else
     rgb5_main(rgb5_lds, q, acc);
-#endif
     rgb5_epi_fwd<EPI>(p, rgb5_lds, acc, n, oy, ox, valid);
-  }
-}
-
-// GDN / IGDN forward at one wave per SIMD: tile i+1's input quads are issued before tile i's epilogue, so the wait
-// for them does not include tile i's stores (vmcnt counts loads and stores together, in order: loaded after the
-// stores, every tile start waited for the previous tile's stores to complete, and the stores never overlapped the
-// MFMAs)
-template <int EPI>
-__global__ __launch_bounds__(256, 1) void conv_rgb5w_x6_kernel(ConvParams p, long ps, int nblk) {
-  extern __shared__ __attribute__((aligned(16))) char rgb5_lds[];
-  rgb5_stage<true>(p, ps, rgb5_lds);
-  const int tiles_x = (p.Wout + 31) / 32, total = tiles_x * p.Hout * p.N, per = (total + nblk - 1) / nblk;
-  int b, cb;
-  xcd_block<true>(b, cb);
-  const int t_end = min(total, b * per + per), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  auto coords = [&](int t, int& n, int& oy, int& ox) {
-    const int tx = t % tiles_x, r = t / tiles_x;
-    oy = r % p.Hout;
-    n = r / p.Hout;
-    ox = tx * 32 + (threadIdx.x & 31);
-  };
-  int t = b * per + wave;
-  if (t >= t_end) return;   // wave-uniform; no barrier follows
-  f32x4 q[RGB5_KY][3];
-  {
-    int n, oy, ox;
-    coords(t, n, oy, ox);
-    rgb5_load(p, n, oy, ox, ox < p.Wout, q);
-  }
-#pragma unroll 1
-  for (; t < t_end; t += 4) {
-    int n, oy, ox;
-    coords(t, n, oy, ox);
-    const bool valid = ox < p.Wout;
-    f32x16 acc[RGB5_IT];
-#pragma unroll
-    for (int it = 0; it < RGB5_IT; ++it) acc[it] = f32x16{0};
-    rgb5_main(rgb5_lds, q, acc);
-    if (t + 4 < t_end) {
-      int n1, oy1, ox1;
-      coords(t + 4, n1, oy1, ox1);
-      rgb5_load(p, n1, oy1, ox1, ox1 < p.Wout, q);
-    }
-    rgb5_epi_fwd_wide<EPI>(p, rgb5_lds, acc, n, oy, ox, valid);
   }
 }
 
@@ -1204,98 +1031,6 @@ ICA_DEV void conv_up_x6_class(const ConvParams& p, const f32x4* patch, int jt, i
   if (u < total) step(fa, fb, ba, bb, u);
 }
 
-#ifdef ICA_MFMA16_AB
-// A/B experiment (timing only; variant builds, scripts/build_variant.sh -DICA_MFMA16_AB): the conv_up_x6 class main
-// loop on v_mfma_f32_16x16x32_bf16.  A K step is 32 deep (a chunk PAIR of one tap); the wave's 128-channel x 64-pixel
-// tile is 8 x 4 blocks of 16 x 16, 6 MFMAs of 16 cycles per block and step: the cycles, operand bytes and register
-// blocking of the 32x32x16 loop (8 row blocks x 3 planes x 1 KB of weights and 4 column blocks x 3 planes of LDS
-// reads per 32 channels).  The weight bytes are the product pack's entries of the two chunks (same addresses, not
-// the 16x16 fragment order) and the accumulators reach the epilogue in the 16x16 block layout: the instruction
-// stream and the traffic are the product's, the values are not.
-ICA_DEV f32x4 mfma16_x6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
-  return c;
-}
-
-template <int PY, int PX, int IT, int CG, int PT, int KS = 5>
-ICA_DEV void conv_up_x6_class16(const ConvParams& p, const f32x4* patch, int jt, int cb, int nch, int grp, long ps,
-                                f32x16 (&acc)[PT][IT]) {
-  constexpr int PAD = KS / 2, XU_PLANE = xu_plane<PT>();
-  constexpr int KY0 = (PY + PAD) & 1, KX0 = (PX + PAD) & 1;
-  constexpr int NY = (KS - KY0 + 1) / 2, NX = (KS - KX0 + 1) / 2, NT = NY * NX;
-  constexpr int NCG = CG / 16, NCP = NCG / 2, RB = 2 * IT, CB = 2 * PT;
-  const int lane = threadIdx.x & 63, q4 = lane >> 4, j16 = lane & 15;
-  const __amdgpu_buffer_rsrc_t wr = uniform_rsrc(p.wp, (unsigned)(3 * ps * 16));
-  const int wbase = cb * KS * KS * nch * IT * 64;
-  const int total = NT * NCP;
-  f32x4 a4[RB][CB];
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-      const int t = c >> 1, it = rb >> 1, k = 2 * (rb & 1) + (c & 1);
-      a4[rb][c] = f32x4{acc[t][it][4 * k], acc[t][it][4 * k + 1], acc[t][it][4 * k + 2], acc[t][it][4 * k + 3]};
-    }
-  auto ldw = [&](bf16x8 (&a)[RB][3], int u) {
-    u = min(u, total - 1);
-    const int ti = u / NCP, cp = u - ti * NCP;
-    const int ky = KY0 + 2 * (ti / NX), kx = KX0 + 2 * (ti % NX);
-    const int f = wbase + ((ky * KS + kx) * nch + grp * NCG + 2 * cp) * IT * 64;
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        a[rb][q] = ld_bf8(wr, lane * 16, (int)((q * ps + f + (rb & 1) * IT * 64 + (rb >> 1) * 64) * 16));
-  };
-  auto ldb = [&](bf16x8 (&b)[CB][3], int u) {
-    u = min(u, total - 1);
-    const int ti = u / NCP, cp = u - ti * NCP;
-    const int ky = KY0 + 2 * (ti / NX), kx = KX0 + 2 * (ti % NX);
-    const int pc = j16 + 1 + (PX + PAD - kx) / 2;
-    const int e = (4 * cp + q4) * XU_PLANE + (jt * 2 * PT + 1 + (PY + PAD - ky) / 2) * XU_PC + pc;
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-      const int o = e + c * XU_PC;
-      b[c][0] = f4_as_bf8(patch[o]);
-      b[c][1] = f4_as_bf8(patch[(CG / 8) * XU_PLANE + o]);
-      b[c][2] = f4_as_bf8(patch[2 * (CG / 8) * XU_PLANE + o]);
-    }
-  };
-  auto step = [&](bf16x8 (&cur)[RB][3], bf16x8 (&nxt)[RB][3], bf16x8 (&bc)[CB][3], bf16x8 (&bn)[CB][3], int u) {
-    ldw(nxt, u + 1);
-    ldb(bn, u + 1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int c = 0; c < CB; ++c)
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb) a4[rb][c] = mfma16_x6(cur[rb], bc[c], a4[rb][c]);
-  };
-  bf16x8 fa[RB][3], fb[RB][3], ba[CB][3], bb[CB][3];
-  ldw(fa, 0);
-  ldb(ba, 0);
-  int u = 0;
-#pragma unroll 1
-  for (; u + 1 < total; u += 2) {
-    step(fa, fb, ba, bb, u);
-    step(fb, fa, bb, ba, u + 1);
-  }
-  if (u < total) step(fa, fb, ba, bb, u);
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int c = 0; c < CB; ++c) {
-      const int t = c >> 1, it = rb >> 1, k = 2 * (rb & 1) + (c & 1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[t][it][4 * k + i] = a4[rb][c][i];
-    }
-}
-#endif
-
 template <int IT, int EPI, int CG, int PT = X6_PT, int KS = 5, int FX = 0>
 __global__ __launch_bounds__(256, 1) void conv_up_x6_kernel(ConvParams p, long ps) {
   ICA_STAMP_BEGIN();
@@ -1361,11 +1096,6 @@ __global__ __launch_bounds__(256, 1) void conv_up_x6_kernel(ConvParams p, long p
       for (int it = 0; it < IT; ++it) acc[t][it] = f32x16{0};
     for (int grp = 0; grp < ngrp; ++grp) {
       if (refill) fill(grp);
-#ifdef ICA_MFMA16_AB
-      if constexpr (KS == 5 && PT == 2 && IT == 4)
-        conv_up_x6_class16<PY, PX, IT, CG, PT, KS>(p, patch, jt, cb, nch, grp, ps, acc);
-      else
-#endif
       conv_up_x6_class<PY, PX, IT, CG, PT, KS>(p, patch, jt, cb, nch, grp, ps, acc);
     }
     ICA_STAMP_AT(tk - 2);
@@ -2226,16 +1956,6 @@ __global__ __launch_bounds__(256, 2) void conv_up3k3_x6_kernel(const float* __re
   }
 }
 
-template <int IT, int EPI, int PT>
-int launch_down_x6_pt(const ConvParams& p, hipStream_t st) {
-  const int tiles = ((p.Wout + XD_TW - 1) / XD_TW) * ((p.Hout + xd_th<PT>() - 1) / xd_th<PT>()) * p.N;
-  const int ncb = (p.Cout + IT * 32 - 1) / (IT * 32);
-  const long ps = (long)ncb * ((((p.Cin + 3) / 4) * 4 + 15) / 16) * 25 * IT * 64;
-  ICA_LAUNCH((conv_down_x6_kernel<IT, EPI, PT>), dim3(tiles, ncb), dim3(256), 0, st, p, ps);
-  ICA_CHECK_LAUNCH();
-  return 0;
-}
-
 // fragments of the order-0 x6 pack per plane, and of the tap-pair extension conv_down_x6w reads (KS = 5, IT = 4)
 static inline long x6_plane_frags(int O, int C, int KS, int IT) {
   return (long)((O + IT * 32 - 1) / (IT * 32)) * ((((C + 3) / 4) * 4 + 15) / 16) * KS * KS * IT * 64;
@@ -2243,6 +1963,16 @@ static inline long x6_plane_frags(int O, int C, int KS, int IT) {
 static inline long x6w_plane_frags(int O, int C) {
   const int nch8 = ((C + 3) / 4 + 1) / 2;
   return (long)((O + 127) / 128) * ((nch8 >> 1) * 25 + (nch8 & 1) * XW_NS) * 4 * 64;
+}
+
+template <int IT, int EPI, int PT>
+int launch_down_x6_pt(const ConvParams& p, hipStream_t st) {
+  const int tiles = ((p.Wout + XD_TW - 1) / XD_TW) * ((p.Hout + xd_th<PT>() - 1) / xd_th<PT>()) * p.N;
+  const int ncb = (p.Cout + IT * 32 - 1) / (IT * 32);
+  ICA_LAUNCH((conv_down_x6_kernel<IT, EPI, PT>), dim3(tiles, ncb), dim3(256), 0, st, p,
+             x6_plane_frags(p.Cout, p.Cin, 5, IT));
+  ICA_CHECK_LAUNCH();
+  return 0;
 }
 
 template <int EPI, int PT>
@@ -2263,8 +1993,8 @@ int launch_down_x6_cs2(const ConvParams& p, hipStream_t st) {
   constexpr int PT = 3;
   const int tiles = ((p.Wout + xd_tw<PT, 2>() - 1) / xd_tw<PT, 2>()) * ((p.Hout + xd_th<PT, 2>() - 1) / xd_th<PT, 2>()) * p.N;
   if (p.Cout != 2 * IT * 32) return -3;
-  const long ps = 2L * ((((p.Cin + 3) / 4) * 4 + 15) / 16) * 25 * IT * 64;
-  ICA_LAUNCH((conv_down_x6_kernel<IT, EPI, PT, 2>), dim3(tiles, 1), dim3(256), 0, st, p, ps);
+  ICA_LAUNCH((conv_down_x6_kernel<IT, EPI, PT, 2>), dim3(tiles, 1), dim3(256), 0, st, p,
+             x6_plane_frags(p.Cout, p.Cin, 5, IT));
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2294,8 +2024,8 @@ template <int IT, int EPI>
 int launch_down_small_x6(const ConvParams& p, hipStream_t st) {
   const int tiles = ((p.Wout + XSD_TW - 1) / XSD_TW) * ((p.Hout + XSD_TH - 1) / XSD_TH) * p.N;
   const int ncb = (p.Cout + IT * 32 - 1) / (IT * 32);
-  const long ps = (long)ncb * ((((p.Cin + 3) / 4) * 4 + 15) / 16) * 25 * IT * 64;
-  ICA_LAUNCH((conv_down_small_x6_kernel<IT, EPI>), dim3(tiles, ncb), dim3(256), 0, st, p, ps);
+  ICA_LAUNCH((conv_down_small_x6_kernel<IT, EPI>), dim3(tiles, ncb), dim3(256), 0, st, p,
+             x6_plane_frags(p.Cout, p.Cin, 5, IT));
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2344,26 +2074,11 @@ int launch_rgb_x6(const ConvParams& p, hipStream_t st) {
   constexpr bool BWD = EPI == EPI_IGDN_BWD || EPI == EPI_GDN_BWD;
   // one persistent block per CU; its waves take consecutive row tiles of a contiguous run
   const int nblk = std::max(1, std::min(ica_cu_count(), (total + (BWD ? 3 : 7)) / (BWD ? 4 : 8)));
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(BWD ? reinterpret_cast<const void*>(&conv_rgb5_bwd_x6_kernel<BWD ? EPI : EPI_IGDN_BWD>)
-                                  : reinterpret_cast<const void*>(&conv_rgb5_x6_kernel<BWD ? EPI_GDN : EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, RGB5_LDS);
-    attr_set = true;
-  }
+  static_assert(RGB5_LDS <= ICA_CU_LDS_BYTES, "conv_rgb5_x6 LDS");
   if constexpr (BWD) {
-    ICA_LAUNCH((conv_rgb5_bwd_x6_kernel<EPI>), dim3(nblk), dim3(256), RGB5_LDS, st, p, ps, nblk);
-  } else if constexpr (RGB5_W && EPI != EPI_BIAS) {
-    const int nb4 = std::max(1, std::min(ica_cu_count(), (total + 3) / 4));
-    static bool attr_w = false;
-    if (!attr_w) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rgb5w_x6_kernel<EPI>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, RGB5_LDS);
-      attr_w = true;
-    }
-    ICA_LAUNCH((conv_rgb5w_x6_kernel<EPI>), dim3(nb4), dim3(256), RGB5_LDS, st, p, ps, nb4);
+    ICA_LAUNCH_LDS((conv_rgb5_bwd_x6_kernel<EPI>), dim3(nblk), dim3(256), RGB5_LDS, st, p, ps, nblk);
   } else {
-    ICA_LAUNCH((conv_rgb5_x6_kernel<EPI>), dim3(nblk), dim3(512), RGB5_LDS, st, p, ps, nblk);
+    ICA_LAUNCH_LDS((conv_rgb5_x6_kernel<EPI>), dim3(nblk), dim3(512), RGB5_LDS, st, p, ps, nblk);
   }
   ICA_CHECK_LAUNCH();
   return 0;
@@ -2374,14 +2089,8 @@ int launch_rgb5_bf16(const ConvParams& p, hipStream_t st) {
   const int total = ((p.Wout + 31) / 32) * p.Hout * p.N;
   const int nblk = std::max(1, std::min(ica_cu_count(), (total + 7) / 8));
   constexpr int lds = rgb5b_lds_bytes<EPI>();
-  static_assert(lds <= 160 * 1024, "conv_rgb5_bf16 LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rgb5_bf16_kernel<EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  ICA_LAUNCH((conv_rgb5_bf16_kernel<EPI>), dim3(nblk), dim3(512), lds, st, p, nblk);
+  static_assert(lds <= ICA_CU_LDS_BYTES, "conv_rgb5_bf16 LDS");
+  ICA_LAUNCH_LDS((conv_rgb5_bf16_kernel<EPI>), dim3(nblk), dim3(512), lds, st, p, nblk);
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2392,14 +2101,8 @@ int launch_up_x6_pt(const ConvParams& p, hipStream_t st) {
   const int ncb = (p.Cout + IT * 32 - 1) / (IT * 32);
   const long ps = (long)ncb * 25 * (p.Cin / 16) * IT * 64;
   constexpr size_t lds = xu_lds_bytes<CG, PT>();
-  static_assert(lds <= 160 * 1024, "conv_up_x6 channel group exceeds LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up_x6_kernel<IT, EPI, CG, PT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  ICA_LAUNCH((conv_up_x6_kernel<IT, EPI, CG, PT>), dim3(tiles, ncb), dim3(256), lds, st, p, ps);
+  static_assert(lds <= ICA_CU_LDS_BYTES, "conv_up_x6 channel group exceeds LDS");
+  ICA_LAUNCH_LDS((conv_up_x6_kernel<IT, EPI, CG, PT>), dim3(tiles, ncb), dim3(256), lds, st, p, ps);
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2413,14 +2116,8 @@ int launch_up_x6w(const ConvParams& p, hipStream_t st) {
   constexpr bool BWD = EPI == EPI_GDN_BWD || EPI == EPI_IGDN_BWD;
   constexpr size_t slabs = BWD ? (size_t)8 * 4 * IT * 64 * sizeof(f32x4) : 0;
   constexpr size_t lds = std::max((size_t)xu_lds_bytes<CG, PT>(), slabs);
-  static_assert(lds <= 160 * 1024, "conv_up_x6w LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up_x6w_kernel<IT, EPI, CG, PT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  ICA_LAUNCH((conv_up_x6w_kernel<IT, EPI, CG, PT>), dim3(tiles, ncb), dim3(512), lds, st, p, ps);
+  static_assert(lds <= ICA_CU_LDS_BYTES, "conv_up_x6w LDS");
+  ICA_LAUNCH_LDS((conv_up_x6w_kernel<IT, EPI, CG, PT>), dim3(tiles, ncb), dim3(512), lds, st, p, ps);
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2438,12 +2135,8 @@ int launch_up_x6(const ConvParams& p, hipStream_t st) {
   // of round 5 took g_a.2.dgrad 3.56 -> 3.63-3.67 ms and 5.83 -> 8.84 GB per launch ((y, s) read twice at PT = 2);
   // for the 32 x 48-input g_a.6.dgrad it is the faster one (0.335 vs 0.41 ms).  PT follows the round fill; each
   // family's PT = 1 and PT = 2 forms give the same bits, and the family depends on the layer only (batch-independent
-  // bits).  ICA_UPW_BWD_ALL builds put every GDN backward on the slab kernel (round 5) for A/B runs.
-#ifdef ICA_UPW_BWD_ALL
-  constexpr bool SLAB = BWD && IT == 4;
-#else
+  // bits).
   constexpr bool SLAB = BWD && IT == 4 && CG == 64;
-#endif
   // PT = 1 forward layers on 64-channel groups (Cin = 192: g_s.0) also take the 8-wave kernel.  On four waves a
   // wave runs its two classes one after the other and each re-stages every group: 6 fills between barriers per block;
   // on eight, one class per wave, each group is staged once (3 fills) and the SIMD partner covers the waits.  Same
@@ -2472,14 +2165,8 @@ int launch_up3s2_x6_pt(const ConvParams& p, hipStream_t st) {
   const int ncb = (p.Cout + IT * 32 - 1) / (IT * 32);
   const long ps = (long)ncb * KS * KS * (p.Cin / 16) * IT * 64;
   constexpr size_t lds = xu_lds_bytes<CG, PT>();
-  static_assert(lds <= 160 * 1024, "conv_up_x6 channel group exceeds LDS");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up_x6_kernel<IT, EPI_BIAS, CG, PT, KS, FX>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  ICA_LAUNCH((conv_up_x6_kernel<IT, EPI_BIAS, CG, PT, KS, FX>), dim3(tiles, ncb), dim3(256), lds, st, p, ps);
+  static_assert(lds <= ICA_CU_LDS_BYTES, "conv_up_x6 channel group exceeds LDS");
+  ICA_LAUNCH_LDS((conv_up_x6_kernel<IT, EPI_BIAS, CG, PT, KS, FX>), dim3(tiles, ncb), dim3(256), lds, st, p, ps);
   ICA_CHECK_LAUNCH();
   return 0;
 }
@@ -2510,14 +2197,8 @@ int launch_up_small_x6(const ConvParams& p, hipStream_t st) {
   const int ncb = (p.Cout + IT * 32 - 1) / (IT * 32);
   const long ps = (long)ncb * 25 * (p.Cin / 16) * IT * 64;
   const size_t lds = (size_t)std::max(3 * (p.Cin / 8) * XSU_PLANE, xs_red_entries<IT>()) * 16;
-  if (lds > 160 * 1024) return -2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up_small_x6_kernel<IT, EPI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  ICA_LAUNCH((conv_up_small_x6_kernel<IT, EPI>), dim3(4 * tiles, ncb), dim3(256), lds, st, p, ps);
+  if (lds > ICA_CU_LDS_BYTES) return -2;
+  ICA_LAUNCH_LDS((conv_up_small_x6_kernel<IT, EPI>), dim3(4 * tiles, ncb), dim3(256), lds, st, p, ps);
   ICA_CHECK_LAUNCH();
   return 0;
 }

@@ -295,15 +295,11 @@ def pack_up3(w_view: torch.Tensor, prec: int = 0) -> Pack:
     w = _weight(w_view)
     Cin = w.shape[0]
     n = int(lib().ica_pack_up3_size(Cin))
-    if prec == PREC_X6:
-        dst = torch.empty(3 * n, dtype=torch.bfloat16, device=w.device)
-        call("ica_pack_up3_x6", ptr(w), ptr(dst), Cin, stream())
-    elif prec:
-        dst = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-        call("ica_pack_up3_bf16", ptr(w), ptr(dst), Cin, stream())
-    else:
+    if prec == PREC_FP32:
         dst = torch.empty(n, device=w.device)
-        call("ica_pack_up3", ptr(w), ptr(dst), Cin, stream())
+    else:
+        dst = torch.empty(3 * n if prec == PREC_X6 else n, dtype=torch.bfloat16, device=w.device)
+    call("ica_pack_up3", ptr(w), ptr(dst), Cin, int(prec), stream())
     return Pack(dst, 3, Cin, 5, ORDER_UP3, prec)
 
 
@@ -477,8 +473,7 @@ def conv_up(x4, Cin, wp: Pack, bias, Cout, epi=EPI_BIAS, gdn: PackedGDN | None =
     N, _, H, W, _ = x4.shape
     y = out if out is not None else empty_nc4(N, 3, 2 * H, 2 * W, x4.device)
     ev = _ev_begin(_prec_note(tag, wp.prec), N)
-    call({PREC_BF16: "ica_conv_up3_bf16", PREC_X6: "ica_conv_up3_x6"}.get(wp.prec, "ica_conv_up3"), ptr(x4), ptr(y),
-         ptr(wp.data), ptr(bias), N, Cin, H, W, int(layout), stream())
+    call("ica_conv_up3", ptr(x4), ptr(y), ptr(wp.data), ptr(bias), N, Cin, H, W, int(layout), int(wp.prec), stream())
     _ev_end(ev)
     return y, None, None
 

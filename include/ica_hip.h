@@ -88,13 +88,6 @@ size_t ica_pack_gdn_x6_size(int C);
 /* bf16 values ica_pack_conv_weight_bf16 writes.  C <= 4 (an RGB conv input; conv_down only) packs "tap groups":
  * k = 8h + j of MFMA tg is tap 4tg + 2h + (j>>2), channel j&3 (7 MFMAs per 32-row tile for 5x5 taps). */
 size_t ica_pack_conv_weight_bf16_size(int O, int C, int KS, int it);
-/* bf16 Z-gather transposed conv to 3 channels (g_s last layer / g_a first-layer input-gradient). */
-/* fp32-accurate bf16x6 conv_up3 (prec 2): three bf16 planes of the ica_pack_up3 fragment order
- * (3 * ica_pack_up3_size(Cin) values); same semantics and argument meaning as ica_conv_up3.  layout: 1 = x is
- * parity-split (ica_conv_args.layout; Cin 128 / 192, even Hin / Win), 0 = row-major. */
-int ica_pack_up3_x6(const float* w, void* dst, int Cin, hipStream_t stream);
-int ica_conv_up3_x6(const float* x, float* y, const void* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                    int layout, hipStream_t stream);
 /* cheng2020 g_a.0 input gradient, fused (replaces the backward of compressai ResidualBlockWithStride(3, N)'s conv1 =
  * conv3x3(3, N, stride 2) and skip = conv1x1(3, N, stride 2), reference anchors/model.py:76-77 -> cheng2020_anchor):
  * dx [N][1][Hout][Wout][4] = conv3x3_s2^T(g1) + conv1x1_s2^T(gs), g1 / gs [N][Cg/4][Hin][Win][4] row-major, Hin =
@@ -104,9 +97,6 @@ int ica_pack_up3k3_x6(const float* w1, const float* ws, void* dst, int Cg, hipSt
 size_t ica_pack_up3k3_x6_size(int Cg);
 int ica_conv_up3k3_x6(const float* g1, const float* gs, const void* wp, float* dx, int N, int Cg, int Hin, int Win,
                       int Hout, int Wout, hipStream_t stream);
-int ica_pack_up3_bf16(const float* w, void* dst, int Cin, hipStream_t stream);
-int ica_conv_up3_bf16(const float* x, float* y, const void* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                      int layout, hipStream_t stream);
 /* bf16 conv path activations are bf16 nChw4c (8 B per channel quad): every prec = 1 conv_down / conv_up reads
  * bf16 x (except 4-channel RGB inputs, fp32), writes bf16 y / save_s and reads bf16 in_x / in_s; the Z-gather
  * kernel reads bf16 x and writes fp32 y.  Casts for the tensors that leave the path (n % 4 == 0): */
@@ -215,7 +205,7 @@ enum { ICA_EPI_LRELU = 6, ICA_EPI_LRELU_BWD = 7 };
 /* Fragment orders of a packed weight (ica_conv_args.order).  DOWN / UP: the `order` argument of the packers (conv_down
  * [cb][chunk][tap], conv_up [cb][tap][chunk]); RGB5: the dense tap-row pack (order 2 of ica_pack_conv_weight_bf16 /
  * _x6); TG: the tap groups ica_pack_conv_weight_bf16 writes for C <= 4 with order 0; UP3: the Z-gather pack of
- * ica_pack_up3* (read by ica_conv_up3* only, never by ica_conv_ex). */
+ * ica_pack_up3 (read by ica_conv_up3 only, never by ica_conv_ex). */
 enum { ICA_ORDER_DOWN = 0, ICA_ORDER_UP = 1, ICA_ORDER_RGB5 = 2, ICA_ORDER_TG = 3, ICA_ORDER_UP3 = 4 };
 typedef struct ica_conv_args {
   const float* x;
@@ -267,12 +257,17 @@ int ica_last_launch(char* name, int cap, unsigned long long* threads);
  * <= 32 x 32 pixels modes 1 / 2 match mode 0 to fp32 rounding only.  Read once per launch (atomic); nothing in the
  * package sets it.  Returns -2 for another mode. */
 int ica_x6_tiling(int mode);
-/* Transposed conv to 3 channels (Z-gather kernel): w view [Cin][3][5][5].  layout: 1 = x parity-split
- * (ica_conv_args.layout bit 0; even Hin / Win), 0 = row-major; the 3-channel output is always row-major. */
+/* Transposed conv to 3 channels (Z-gather kernel; g_s's last layer, deconv(N, 3) of anchors/utils.py:122-130, and the
+ * input gradient of g_a's first, conv(3, N) of anchors/utils.py:112-119): w view [Cin][3][5][5], Cin % 16 == 0.
+ * prec as ica_conv_args.prec, for the pack and the launch alike (another value returns -4 before any device call):
+ * 0 = fp32 (dst: ica_pack_up3_size(Cin) floats); 1 = bf16 operands (dst: as many bf16; x is bf16 nChw4c, y fp32);
+ * 2 = fp32-accurate bf16x6 (dst: three bf16 planes of the fp32 fragment order, 3 * ica_pack_up3_size(Cin) values).
+ * layout: 1 = x parity-split (ica_conv_args.layout bit 0; even Hin / Win), 0 = row-major; the 3-channel output is
+ * always row-major. */
 size_t ica_pack_up3_size(int Cin);
-int ica_pack_up3(const float* w, float* dst, int Cin, hipStream_t stream);
-int ica_conv_up3(const float* x, float* y, const float* wp, const float* bias, int N, int Cin, int Hin, int Win,
-                 int layout, hipStream_t stream);
+int ica_pack_up3(const float* w, void* dst, int Cin, int prec, hipStream_t stream);
+int ica_conv_up3(const float* x, float* y, const void* wp, const float* bias, int N, int Cin, int Hin, int Win,
+                 int layout, int prec, hipStream_t stream);
 
 /* ---- elementwise / attack step / entropy (ica_elem.hip) -------------------- */
 int ica_elem_blocks_per_image(void);

@@ -285,3 +285,17 @@ def test_b1_precision_code_documented():
     assert "3: bf16 operands over fp32 tensors on the k3 conv_downs" in hdr
     from imagecompression_adversarial_amd.engine_cheng import _it, X6_IT
     assert _it(128) in X6_IT and _it(192) in X6_IT   # N = 128 and 192 both get the x6 / one-plane packs
+
+
+def test_up3_refuses_unknown_precision_before_any_device_call():
+    """The Z-gather entry points validate before they touch the device: prec = 7 (ica_conv_args.prec knows 0, 1, 2
+    here) with otherwise valid sizes and null pointers returns -4 from ica_conv_up3 and ica_pack_up3, and
+    ica_last_launch afterwards reports no launch."""
+    import ctypes as C
+    from imagecompression_adversarial_amd import _lib
+    L = _lib.lib()
+    name, thr = C.create_string_buffer(256), C.c_ulonglong(0)
+    L.ica_last_launch(name, 256, C.byref(thr))   # consume whatever an earlier test of this process launched
+    assert L.ica_conv_up3(None, None, None, None, 1, 128, 4, 4, 0, 7, None) == -4
+    assert L.ica_pack_up3(None, None, 128, 7, None) == -4
+    assert L.ica_last_launch(name, 256, C.byref(thr)) == 0
