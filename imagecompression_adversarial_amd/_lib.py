@@ -87,6 +87,10 @@ _SIGS = {
     # latent distribution: per-channel histogram, predicted distribution, bits (ica_distrib.hip)
     "ica_latent_distrib_ws_size": [_i, _i, _i, _i, _i],
     "ica_latent_distrib": [_p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _p, _p],
+    # layer-wise error propagation: the sums of every layer of a side in one launch (ica_layers.hip)
+    "ica_layer_sums_blocks": [_i, _i, _i],
+    "ica_layer_sums_ws_size": [_i, _i],
+    "ica_layer_sums": [_p, _i, _i, _p, _p, _p],
     # bitrate attack: entropy-model value gradients (ica_rate.hip)
     "ica_rate_gc_blocks": [],
     "ica_rate_eb_blocks": [_i, _i, _i],
@@ -165,7 +169,8 @@ _RESTYPES = {"ica_pack_conv_weight_size": _sz, "ica_pack_conv_weight_bf16_size":
              "ica_rans_encode": _l, "ica_ar_lds_bytes": _sz, "ica_patch_vi_ws_size": _sz,
              "ica_gauss_blur_ws_size": _sz, "ica_blur_sweep_ws_size": _sz, "ica_noise_apply_ws_size": _sz,
              "ica_transfer_apply_ws_size": _sz, "ica_transfer_score_ws_size": _sz,
-             "ica_requant8_ws_size": _sz, "ica_floor_bits_ws_size": _sz, "ica_latent_distrib_ws_size": _sz}
+             "ica_requant8_ws_size": _sz, "ica_floor_bits_ws_size": _sz, "ica_latent_distrib_ws_size": _sz,
+             "ica_layer_sums_ws_size": _sz}
 
 
 
@@ -183,6 +188,11 @@ class ArArgs(C.Structure):
                                             "b1", "w2", "b2", "w3", "b3", "table")]
                 + [("T", C.c_int), ("bound", C.c_float)]
                 + [(n, C.c_int) for n in ("B", "M", "H", "W", "E1", "E2")])
+
+
+class LayerDesc(C.Structure):
+    """include/ica_hip.h ica_layer_desc."""
+    _fields_ = [(n, C.c_void_p) for n in ("a", "b", "c")] + [(n, C.c_int) for n in ("C", "H", "W", "mode")]
 
 
 _lib = None

@@ -82,6 +82,9 @@ class Analysis:
                       for i in (0, 2, 4, 6)]
         self.gdns = [K.PackedGDN(_P(sd, prefix, f"{i}.beta"), _P(sd, prefix, f"{i}.gamma")) for i in (1, 3, 5)]
         self.split = _split_policy(self.convs)
+        # the conv weights themselves (references, no copies): layer_study packs a 6-tile GDN layer once more for
+        # its bias-epilogue launch, which the 6-tile conv_down kernels do not have
+        self.weights = [_P(sd, prefix, f"{i}.weight") for i in (0, 2, 4, 6)]
 
     def forward(self, x4, save=False, split=None):
         """split: which inner levels (L1, L2, L3) to store parity-split (True / False / per-level flags; default

@@ -10,7 +10,7 @@ import math
 
 import torch
 
-from ._lib import ConvArgs, call, lib, ptr, stream
+from ._lib import ConvArgs, LayerDesc, call, lib, ptr, stream
 
 EPI_BIAS, EPI_RELU, EPI_GDN, EPI_IGDN, EPI_GDN_BWD, EPI_IGDN_BWD, EPI_LRELU, EPI_LRELU_BWD = range(8)
 FILL_PLAIN, FILL_LRELU_MASK, FILL_UNSHUFFLE = range(3)
@@ -763,6 +763,59 @@ def val_metrics(x_hat4: torch.Tensor, target: torch.Tensor, lik_y4: torch.Tensor
     _rd_status("ica_val_metrics", rc)
     sums = reduce_rows(part, 3 * B).view(B, 3)
     return sums[:, 0], sums[:, 1], sums[:, 2], out
+
+
+# --------------------------------------------------------------------------- #
+# Layer-wise error propagation: the sums of every layer of a side in one launch (ica_layers.hip)
+# --------------------------------------------------------------------------- #
+LAYER_PAIR, LAYER_QUANT, LAYER_TRIPLE = 0, 1, 2
+LAYERS_MAX = 16
+
+
+def layer_sums(layers, B: int) -> torch.Tensor:
+    """sums [n, B, 2] of n <= LAYERS_MAX layers in one launch (ica_layer_sums + ica_reduce_rows).  A layer is
+    (mode, C, a, b[, c]): fp32 nChw4c tensors [B, ceil(C/4), H, W, 4] of one shape, each a contiguous run of B
+    images (a slice of a larger batch along dim 0 is one), all in one storage layout.
+      LAYER_PAIR    sum (a - b)^2, 0
+      LAYER_QUANT   sum (a - round(b))^2, sum (round(a) - round(b))^2
+      LAYER_TRIPLE  sum (a - c)^2, sum (b - c)^2
+    Anything else is a ValueError and launches nothing."""
+    positive_int("B", B)
+    if not 1 <= len(layers) <= LAYERS_MAX:
+        raise ValueError(f"layer_sums takes 1 .. {LAYERS_MAX} layers, not {len(layers)}")
+    arr = (LayerDesc * len(layers))()
+    dev = None
+    for i, (mode, C, a, b, *rest) in enumerate(layers):
+        if mode not in (LAYER_PAIR, LAYER_QUANT, LAYER_TRIPLE):
+            raise ValueError(f"layer {i}: unknown mode {mode!r}")
+        c = rest[0] if rest else None
+        if (c is None) == (mode == LAYER_TRIPLE):
+            raise ValueError(f"layer {i}: the triple mode, and only it, reads a third tensor")
+        positive_int(f"layer {i}: C", C)
+        for t in (a, b, c):
+            if t is None:
+                continue
+            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
+                    or t.dim() != 5 or t.shape[0] != B or t.shape[1] != c4(C) or t.shape[4] != 4
+                    or t.shape != a.shape or t.device != a.device):
+                what = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"layer {i}: {what} is not a contiguous float32 HIP nChw4c tensor of {B} images and "
+                                 f"{C} channels, shaped like the layer's first")
+        dev = a.device if dev is None else dev
+        if a.device != dev:
+            raise ValueError(f"layer {i} is on {a.device}, layer 0 on {dev}")
+        arr[i] = LayerDesc(a.data_ptr(), b.data_ptr(), None if c is None else c.data_ptr(), C, a.shape[2],
+                           a.shape[3], mode)
+    n = len(layers)
+    ws = int(lib().ica_layer_sums_ws_size(n, B))
+    if ws == 0:
+        raise ValueError(f"ica_layer_sums does not take n, B = {(n, B)}")
+    work = torch.empty(ws, dtype=torch.float32, device=dev)
+    sums = torch.empty((n, B, 2), dtype=torch.float32, device=dev)
+    import ctypes
+    rc = lib().ica_layer_sums(ctypes.cast(arr, ctypes.c_void_p), n, B, ptr(sums), ptr(work), stream())
+    _rd_status("ica_layer_sums", rc)
+    return sums
 
 
 # --------------------------------------------------------------------------- #

@@ -416,6 +416,35 @@ int ica_latent_distrib(const float* y4, const float* scales4, const float* means
                        int H, int W, float vmin, int nbins, float scale_floor, float pred_floor, int* hist,
                        float* pred, float* bits, float* work, hipStream_t stream);
 
+/* ---- layer-wise error propagation (ica_layers.hip) ----------------------------
+ * The sums behind layer_compare (anchors/utils.py:132-166) for every layer of a side in one launch.  A descriptor
+ * names up to three fp32 nChw4c tensors [B][ceil(C/4)][H][W][4] (16-byte aligned, each a contiguous run of B images:
+ * the halves or thirds of one batched forward) and a mode; per (layer, image) two sums come back, sums[layer][B][2]:
+ *   ICA_LAYER_PAIR    sum (a - b)^2,        0                         (c ignored)
+ *   ICA_LAYER_QUANT   sum (a - rne(b))^2,   sum (rne(a) - rne(b))^2   (c ignored; rne = round half to even, the
+ *                                                                      bits of torch.round; nothing rounded is stored)
+ *   ICA_LAYER_TRIPLE  sum (a - c)^2,        sum (b - c)^2             (c read once)
+ * The tensors of a descriptor must share one storage layout (row-major or the parity-split order of
+ * ica_conv_args.layout): the sums run over whole planes, so which of the two does not change what is summed.
+ * Padding lanes (c >= C) add nothing whatever they hold.  layers is a HOST array of n <= ICA_LAYERS_MAX descriptors,
+ * copied into the kernel arguments (no device table).  work: scratch of ica_layer_sums_ws_size(n, B) floats.
+ * Fixed-order sums (ica_reduce.h, then ica_reduce_rows), no float atomics, and the ica_layer_sums_blocks(C, H, W)
+ * partials of an image are a function of the layer's size alone: an image's numbers are the same bits alone and in
+ * a batch, with any other layers in the table, run to run.  Status: 0; -5 for n outside 1 .. 16, B outside
+ * 1 .. 65535, an unknown mode, C / H / W <= 0, more than 2^31 - 1 channel quads an image or 2^47 elements a tensor, a missing or
+ * misaligned pointer; -7 for an output that overlaps an input or the other output.  Nothing is launched then. */
+enum { ICA_LAYER_PAIR = 0, ICA_LAYER_QUANT = 1, ICA_LAYER_TRIPLE = 2 };
+enum { ICA_LAYERS_MAX = 16 };
+typedef struct ica_layer_desc {
+  const float* a;
+  const float* b;
+  const float* c;
+  int C, H, W, mode;
+} ica_layer_desc;
+int ica_layer_sums_blocks(int C, int H, int W);
+size_t ica_layer_sums_ws_size(int n, int B);
+int ica_layer_sums(const ica_layer_desc* layers, int n, int B, float* sums, float* work, hipStream_t stream);
+
 /* ---- bitrate attack: entropy-model value gradients (ica_rate.hip) -----------
  * The expensive branch of attack_rd -r minimises  L = scale * sum ln lik  (scale = 1 / (ln 2 * H_img * W_img) > 0,
  * so L = -bpp of the relaxed codec): the train-mode likelihoods of the UNROUNDED latents with zero noise
