@@ -150,8 +150,30 @@ def code(args, net, input_file, out_file=None):
     return result
 
 
+class JpegMethod(str):
+    """The ``--defend_m`` value "jpeg" together with the round trip's settings.  It compares, hashes and prints as
+    the plain string, so every CLI that hands ``args.method`` on (batch_test does, to rd_eval.rd_eval_defended) hands
+    ``--jpeg-quality`` and ``--jpeg-subsampling`` on with it."""
+
+    def __new__(cls, quality=50, subsampling="420"):
+        self = super().__new__(cls, "jpeg")
+        self.quality, self.subsampling = quality, subsampling
+        return self
+
+    def __getnewargs__(self):
+        return (self.quality, self.subsampling)
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if getattr(ns, "method", None) == "jpeg":
+            ns.method = JpegMethod(ns.jpeg_quality, ns.jpeg_subsampling)
+        return ns, rest
+
+
 def config():
-    p = argparse.ArgumentParser()
+    p = _Parser()
     p.add_argument("-device", type=str, default="cuda:0", help="dev id")
     p.add_argument("-lr_train", dest="lr_train", type=float, default=0.0001, help="train learning rate")
     p.add_argument("-lamb", dest="lamb", type=float, default=None, help="training lambda")
@@ -211,4 +233,9 @@ def config():
                         "vs float64 no larger than the fp32-operand path's), fp32 (fp32-operand MFMA; the debug "
                         "model's only one) or bf16 (bf16 operands, fp32 accumulate; BASELINE config 5; cheng2020: "
                         "over fp32 activations)")
+    p.add_argument("--jpeg-quality", dest="jpeg_quality", type=int, default=50,
+                   help="-degrade jpeg / --defend_m jpeg: quality of the JPEG round trip, 1 .. 100 (default 50, the q "
+                        "of test_commands/jpeg.sh)")
+    p.add_argument("--jpeg-subsampling", dest="jpeg_subsampling", type=str, default="420", choices=("420", "444"),
+                   help="-degrade jpeg / --defend_m jpeg: chroma subsampling (default 420, cjpeg's)")
     return p

@@ -5,7 +5,7 @@
 //                        per-image mean((out - ref)^2)
 //   blur_sweep_kernel    the sigma scan of generate_blurimages (random_noise.py:59-63): mean((clamp(blur_s(x)) - x)^2)
 //                        of up to SWEEP_CHUNK candidate kernels per launch from one staged tile, no image written
-//   sweep_select_kernel  per image the first candidate of the chunk with mse <= budget, and the per-image done flag
+//   sweep_select_kernel  (ica_reduce.h) per image the first candidate of the chunk with mse <= budget, and the done flag
 //   noise_apply_kernel   random_noise.py:80: clamp(im + noise, 0, 1), mean(noise^2) and mean((im_in - im)^2)
 //
 // Arithmetic (fp32, DESIGN.md "Degradations"): the 2-D weight of tap (i, j) is the single rounded product
@@ -192,33 +192,6 @@ __global__ __launch_bounds__(DG_THREADS) void blur_sweep_kernel(const float* __r
   }
 }
 
-// one block: per unfinished image the first candidate of this chunk with mse <= budget; remaining[0] = images still
-// without an answer
-__global__ __launch_bounds__(DG_THREADS) void sweep_select_kernel(const float* __restrict__ mse, long ld, int s0, int S,
-                                                                  float budget, int B, int* __restrict__ idx,
-                                                                  int* __restrict__ done,
-                                                                  int* __restrict__ remaining) {
-  __shared__ int left;
-  if (threadIdx.x == 0) left = 0;
-  __syncthreads();
-  int mine = 0;
-  for (int b = threadIdx.x; b < B; b += DG_THREADS) {
-    if (done[b]) continue;
-    int found = -1;
-    for (int s = 0; s < S && found < 0; ++s)
-      if (mse[(size_t)b * ld + s0 + s] <= budget) found = s0 + s;
-    if (found >= 0) {
-      idx[b] = found;
-      done[b] = 1;
-    } else {
-      ++mine;
-    }
-  }
-  if (mine) atomicAdd(&left, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) remaining[0] = left;
-}
-
 __global__ __launch_bounds__(DG_THREADS) void noise_apply_kernel(const float* __restrict__ im,
                                                                  const float* __restrict__ noise,
                                                                  float* __restrict__ out, long quads,
@@ -316,7 +289,7 @@ int ica_blur_sweep(const float* x, const float* wx, const float* wy, int S, int 
   ICA_CHECK_LAUNCH();
   finish_rows(st, ws, B * S, 3 * tiles_of(H, W), (float)((long)3 * H * W), mse, S, ld, s0, done);
   ICA_CHECK_LAUNCH();
-  ICA_LAUNCH(sweep_select_kernel, dim3(1), dim3(DG_THREADS), 0, st, (const float*)mse, ld, s0, S, budget, B, idx, done,
+  ICA_LAUNCH(sweep_select_kernel, dim3(1), dim3(SELECT_THREADS), 0, st, (const float*)mse, ld, s0, S, budget, B, idx, done,
              remaining);
   ICA_CHECK_LAUNCH();
   return 0;

@@ -71,6 +71,35 @@ __global__ __launch_bounds__(64) void finish_rows_kernel(const float* __restrict
   if (threadIdx.x == 0) out[(size_t)img * ld + off + (row - img * rpi)] = fdiv_rn(s, count);
 }
 
+constexpr int SELECT_THREADS = 256;
+
+// The first-fit step of a budget sweep (ica_degrade.hip's sigma scan, ica_jpeg.hip's quality scan).  One block: per
+// unfinished image the first candidate of this chunk with mse <= budget; remaining[0] = images still without an answer
+__global__ __launch_bounds__(SELECT_THREADS) void sweep_select_kernel(const float* __restrict__ mse, long ld, int s0,
+                                                                      int S, float budget, int B,
+                                                                      int* __restrict__ idx, int* __restrict__ done,
+                                                                      int* __restrict__ remaining) {
+  __shared__ int left;
+  if (threadIdx.x == 0) left = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int b = threadIdx.x; b < B; b += SELECT_THREADS) {
+    if (done[b]) continue;
+    int found = -1;
+    for (int s = 0; s < S && found < 0; ++s)
+      if (mse[(size_t)b * ld + s0 + s] <= budget) found = s0 + s;
+    if (found >= 0) {
+      idx[b] = found;
+      done[b] = 1;
+    } else {
+      ++mine;
+    }
+  }
+  if (mine) atomicAdd(&left, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) remaining[0] = left;
+}
+
 inline void finish_rows(hipStream_t st, const float* part, int rows, int n, float count, float* out, int rpi = 1,
                         long ld = 1, long off = 0, const int* done = nullptr) {
   ICA_LAUNCH(finish_rows_kernel, dim3(rows), dim3(64), 0, st, part, n, count, out, rpi, ld, off, done);

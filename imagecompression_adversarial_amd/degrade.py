@@ -8,6 +8,11 @@ blur_to_budget    generate_blurimages: the first sigma of the schedule whose cla
 apply_noise       random_noise.py:80: clamp(im + noise, 0, 1), mean(noise^2), mean((im_in - im)^2)
 evaluate_noise    test (random_noise.py:68-111), per image
 evaluate_deblur   test_deblur (random_noise.py:20-48), per image
+jpeg_tables       the T.81 Annex K tables scaled by the IJG rule, as integers on the host
+jpeg_roundtrip    the baseline-JPEG transform round trip (ica_jpeg.hip; DESIGN.md "JPEG round trip"): what
+                  test_commands/jpeg.sh makes with ``cjpeg -q 50``, and the input-transformation defence
+jpeg_to_budget    the first quality from 1 upward whose round trip fits the MSE budget
+evaluate_jpeg     test's numbers with the JPEG error in the place of the noise
 
 All image tensors are the planar NCHW fp32 [B, 3, H, W] device tensors attack.evaluate holds.  The sigma scan is a
 linear scan on purpose: a normalised 5-tap Gaussian's side tap is not monotone in sigma, so neither is the MSE, and
@@ -17,6 +22,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from functools import lru_cache
 
 import torch
 
@@ -75,6 +81,123 @@ def validate(H, W, kernel_size=BLUR_KSIZE, sigma=BLUR_SIGMA, noise=None, factor=
             raise ValueError(f"the schedule start={start!r}, step={step!r} is empty")
         if start / step > 1e6:
             raise ValueError(f"the schedule start={start!r}, step={step!r} has more than 1e6 candidates")
+
+
+# ITU-T T.81 Annex K, tables K.1 (luminance) and K.2 (chrominance), row-major: row = vertical frequency
+JPEG_LUMA = (16, 11, 10, 16, 24, 40, 51, 61,
+             12, 12, 14, 19, 26, 58, 60, 55,
+             14, 13, 16, 24, 40, 57, 69, 56,
+             14, 17, 22, 29, 51, 87, 80, 62,
+             18, 22, 37, 56, 68, 109, 103, 77,
+             24, 35, 55, 64, 81, 104, 113, 92,
+             49, 64, 78, 87, 103, 121, 120, 101,
+             72, 92, 95, 98, 112, 100, 103, 99)
+JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99,
+               18, 21, 26, 66, 99, 99, 99, 99,
+               24, 26, 56, 99, 99, 99, 99, 99,
+               47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+JPEG_QUALITY, JPEG_SUBSAMPLING = 50, "420"     # test_commands/jpeg.sh: cjpeg -q 50, cjpeg's default subsampling
+JPEG_MCU = {"420": 16, "444": 8}
+
+
+def validate_jpeg(H=None, W=None, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING, noise=None,
+                  factor=SWEEP_FACTOR):
+    """ValueError unless ica_jpeg_roundtrip / ica_jpeg_sweep take this problem (include/ica_hip.h).  ``quality``: one
+    value or a list; H, W None checks the flags alone."""
+    if subsampling not in JPEG_MCU:
+        raise ValueError(f"subsampling {subsampling!r} is not one of {sorted(JPEG_MCU)}")
+    for q in (quality if isinstance(quality, (tuple, list)) else [quality]):
+        if isinstance(q, bool) or not isinstance(q, int) or q < 1 or q > 100:
+            raise ValueError(f"a JPEG quality is an integer in 1 .. 100, got {q!r}")
+    if H is not None:
+        K.positive_int("H", H)
+        K.positive_int("W", W)
+        mcu = JPEG_MCU[subsampling]
+        if H % mcu or W % mcu:
+            raise ValueError(f"the image {H}x{W} is not a multiple of the {mcu}x{mcu} MCU of subsampling {subsampling}")
+    if noise is not None:
+        if isinstance(noise, bool) or not isinstance(noise, (int, float)) or not math.isfinite(noise) or noise <= 0:
+            raise ValueError(f"noise must be a positive finite number, got {noise!r}")
+        if not factor > 0 or not math.isfinite(factor):
+            raise ValueError(f"factor must be positive, got {factor!r}")
+
+
+def jpeg_tables(q):
+    """(luminance [64], chrominance [64]) as lists of ints: the Annex K tables scaled by the IJG rule, s = 5000 // q
+    below 50, else 200 - 2 q; each entry clamp((base * s + 50) // 100, 1, 255)."""
+    validate_jpeg(quality=q)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple([min(max((v * s + 50) // 100, 1), 255) for v in base] for base in (JPEG_LUMA, JPEG_CHROMA))
+
+
+@lru_cache(maxsize=64)
+def _jpeg_tabs(qualities, device):
+    """[len(qualities), 128] fp32 on ``device``: row i is the table pair of qualities[i] (every entry an exact small
+    integer).  Cached per (qualities, device), so a repeated round trip pays no host-to-device copy."""
+    return torch.tensor([sum(jpeg_tables(q), []) for q in qualities], dtype=torch.float32).to(device)
+
+
+def _jpeg_ws(name, B, H, W, sub, dev):
+    return torch.empty(getattr(lib(), name)(B, H, W, sub), dtype=torch.float32, device=dev)
+
+
+def jpeg_roundtrip(x, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING, ref=None):
+    """The JPEG round trip of clamp(x, 0, 1) at ``quality`` (an int, or one per image).  With ``ref`` returns
+    (image, mean((image - ref)^2) [B]), else the image."""
+    B, H, W = K.check_image(x, "x")
+    qs = list(quality) if isinstance(quality, (tuple, list)) else [quality] * B
+    validate_jpeg(H, W, qs, subsampling)
+    if len(qs) != B:
+        raise ValueError(f"{len(qs)} qualities for a batch of {B}")
+    if ref is not None:
+        if ref.shape != x.shape:
+            raise ValueError(f"ref {tuple(ref.shape)} differs from x {tuple(x.shape)}")
+        K._dev_check(ref, "ref")
+    sub = int(subsampling)
+    tabs = _jpeg_tabs(tuple(qs), str(x.device))
+    out = torch.empty_like(x)
+    mse = torch.empty(B, dtype=torch.float32, device=x.device) if ref is not None else None
+    ws = _jpeg_ws("ica_jpeg_roundtrip_ws_size", B, H, W, sub, x.device)
+    call("ica_jpeg_roundtrip", ptr(x), ptr(tabs), B, H, W, sub, ptr(ref), ptr(out), ptr(mse), ptr(ws), stream())
+    return out if ref is None else (out, mse)
+
+
+def jpeg_sweep(x, noise, factor=SWEEP_FACTOR, subsampling=JPEG_SUBSAMPLING):
+    """Scores the qualities 1, 2, .. 100 in that order (the strongest degradation first), a chunk per launch, until
+    every image has its first fit: (index [B] int32 on the device, quality index + 1, -1 where none fits; mse
+    [B, 100] against x itself, NaN where a candidate was not needed).  A linear scan: JPEG's MSE is not monotone
+    in the quality."""
+    B, H, W = K.check_image(x, "x")
+    validate_jpeg(H, W, JPEG_QUALITY, subsampling, noise, factor)
+    dev, sub, n = x.device, int(subsampling), 100
+    tabs = _jpeg_tabs(tuple(range(1, n + 1)), str(dev))
+    mse = torch.full((B, n), float("nan"), dtype=torch.float32, device=dev)
+    idx = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    done = torch.zeros(B, dtype=torch.int32, device=dev)
+    remaining = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = _jpeg_ws("ica_jpeg_sweep_ws_size", B, H, W, sub, dev)
+    chunk = lib().ica_jpeg_sweep_chunk()
+    for s0 in range(0, n, chunk):
+        S = min(chunk, n - s0)
+        call("ica_jpeg_sweep", ptr(x), ptr(tabs[s0:]), S, B, H, W, sub, float(factor * noise), s0, ptr(mse), n,
+             ptr(idx), ptr(done), ptr(remaining), ptr(ws), stream())
+        if int(remaining.item()) == 0:   # the one host read per chunk
+            break
+    return idx, mse
+
+
+def jpeg_to_budget(x, noise, factor=SWEEP_FACTOR, subsampling=JPEG_SUBSAMPLING):
+    """(round trip at the first quality from 1 upward with mse <= factor * noise, quality [B] int64 (0 where none
+    fits), index [B] int32, mse [B]).  An image no quality fits has index -1 and comes back unchanged with mse 0."""
+    idx, _ = jpeg_sweep(x, noise, factor, subsampling)
+    k = idx.cpu()
+    hit = k >= 0
+    out, mse = jpeg_roundtrip(x, [i + 1 if i >= 0 else 100 for i in k.tolist()], subsampling, ref=x)
+    if not bool(hit.all()):
+        miss = (~hit).to(x.device)
+        out[miss] = x[miss]
+        mse[miss] = 0.0
+    return out, (k + 1).to(torch.int64), k, mse
 
 
 def _ws(name, B, H, W, dev):
@@ -216,6 +339,31 @@ def evaluate_noise(kern, im, noise, num_pixels=None):
         psnr=[-_db(e) for e in err_im],
         bpp_ori=[bpp[b] * scale[b] for b in range(B)],
         noise_power=power_l, mse_in=mse_in.tolist(), err_out=err_out, x_hat=x_hat, im_in=im_in)
+
+
+def evaluate_jpeg(kern, im_jpeg, im, num_pixels=None):
+    """test's numbers (random_noise.py:68-111) per image with the JPEG error in the place of the noise:
+    noise_power = mse_in = mean((im_jpeg - im)^2), so dpsnr = 10 log10(err_out / mse_in) compares directly with the
+    noise baseline and with an attack's VI.  One eval forward over [im; im_jpeg]."""
+    from .attack import eval_forward
+    B, H, W = K.check_image(im, "im")
+    if im_jpeg.shape != im.shape:
+        raise ValueError(f"im_jpeg {tuple(im_jpeg.shape)} differs from im {tuple(im.shape)}")
+    K._dev_check(im_jpeg, "im_jpeg")
+    out, bpp = eval_forward(kern, torch.cat([im, im_jpeg], 0), True)
+    x_hat_ori, x_hat = out[:B].contiguous(), out[B:].contiguous()
+    mse_in = K.sqdiff_mean(im_jpeg, im).tolist()
+    err_out = K.sqdiff_mean(x_hat_ori, x_hat).tolist()
+    err_im = K.sqdiff_mean(x_hat, im).tolist()
+    npx = [H * W] * B if num_pixels is None else ([num_pixels] * B if isinstance(num_pixels, int) else list(num_pixels))
+    scale = [H * W / n for n in npx]
+    bpp = bpp.tolist()
+    return NoiseResult(
+        dpsnr=[_db(e / p) if p > 0 else float("nan") for e, p in zip(err_out, mse_in)],
+        bpp=[bpp[B + b] * scale[b] for b in range(B)],
+        psnr=[-_db(e) for e in err_im],
+        bpp_ori=[bpp[b] * scale[b] for b in range(B)],
+        noise_power=mse_in, mse_in=list(mse_in), err_out=err_out, x_hat=x_hat, im_in=im_jpeg)
 
 
 def evaluate_deblur(kern, im_blur, im_sharp):

@@ -16,6 +16,7 @@ Defended evaluation follows test.py, not self_ensemble.eval: every method is sco
   resize   : net(random_resize(x, 243 / 256))  (an image whose size the resize changes raises, as the reference's
              mse would)
   range    : the latent clamp of attack_rd.py:263-268 through forward(latent=...) (an extension, as in self_ensemble)
+  jpeg     : net(degrade.jpeg_roundtrip(x, quality, subsampling))  (an extension: the JPEG input transformation)
 
 Deviations from test.py (DESIGN.md "RD evaluation"): images whose smaller side is <= 160 get msim = msim_dB = nan
 (pytorch_msssim raises there); msim == 1 gives msim_dB = inf instead of the reference's math domain error; psnr and
@@ -31,7 +32,7 @@ import torch
 from . import hip_ops as K
 from . import msssim as MS
 
-METHODS = ("ensemble", "bitdepth", "resize", "range")
+METHODS = ("ensemble", "bitdepth", "resize", "range", "jpeg")
 MSSSIM_MIN_SIDE = 160   # pytorch_msssim: min(H, W) > (11 - 1) * 2 ** 4
 
 
@@ -145,11 +146,17 @@ def _eval_ensemble(kern, x, real_bpp_net, msssim):
     return _cat(out, best)
 
 
-def rd_eval_defended(kern, x, method="ensemble", profile=None, real_bpp_net=None, msssim=True) -> RDResult:
+def rd_eval_defended(kern, x, method="ensemble", profile=None, real_bpp_net=None, msssim=True, jpeg=None) -> RDResult:
     """test.py's evaluation with --defend (test.py:37-49), per image, scored against the original ``x``.
-    profile: the latent_range.RangeProfile of method 'range'."""
+    profile: the latent_range.RangeProfile of method 'range'; jpeg: (quality, subsampling) of method 'jpeg'
+    (None: what a coder.JpegMethod carries, as batch_test passes it, else (50, "420"))."""
     if method not in METHODS:
         raise ValueError(f"defend method {method!r} not in {METHODS}")
+    if method == "jpeg":
+        from . import degrade
+        jpeg = jpeg or (getattr(method, "quality", degrade.JPEG_QUALITY),
+                        getattr(method, "subsampling", degrade.JPEG_SUBSAMPLING))
+        degrade.validate_jpeg(quality=jpeg[0], subsampling=jpeg[1])
     x, B, H, W = _check_batch(x)
     if method == "ensemble":
         return _eval_ensemble(kern, x, real_bpp_net, msssim)
@@ -162,7 +169,7 @@ def rd_eval_defended(kern, x, method="ensemble", profile=None, real_bpp_net=None
         res = kern.forward(K.to_nc4(x), latent=lambda y4: latent_clamp(y4, kern.M, profile))
         return score(kern, res, x, msssim)
     from . import self_ensemble as SE
-    xp = SE.defend(kern, x, method)
+    xp = SE.defend(kern, x, method, jpeg)
     if xp.shape != x.shape:
         raise RuntimeError(f"defend '{method}' changed the image size {tuple(x.shape)} -> {tuple(xp.shape)} (the "
                            f"reference's mse against the original fails the same way)")

@@ -1,7 +1,7 @@
 """Eval-time defences of the reference's self_ensemble.py on the HIP kernels.
 
     python -m imagecompression_adversarial_amd.self_ensemble -m hyper -q 3 -metric mse -s 'kodim*.png' \\
-        --defend --defend_m ensemble|resize|bitdepth
+        --defend --defend_m ensemble|resize|bitdepth|jpeg
 
 rotates             self_ensemble.py:34-57   8 dihedral variants / their inverses (ica_flip_rot)
 bitdepth_reduction  self_ensemble.py:59-70   round(x * (2^bits - 1)) / (2^bits - 1)   (ica_bitdepth)
@@ -199,11 +199,22 @@ def self_ensemble(kern, x):
     return best_mse, best_x, best_idx
 
 
-def defend(kern, x, method="ensemble"):
-    """self_ensemble.defend: the preprocessed input the eval encodes (and, for 'ensemble', the variants)."""
-    assert method in ("ensemble", "resize", "bitdepth"), f"{method} not in 'ensemble', 'resize'"
+JPEG_ADV_REASON = ("the attack through the JPEG defence is not built: the round trip's roundings have no gradient, and "
+                   "a straight-through variant is a separate piece of work")
+
+
+def defend(kern, x, method="ensemble", jpeg=None):
+    """self_ensemble.defend: the preprocessed input the eval encodes (and, for 'ensemble', the variants).  'jpeg' (an
+    extension): degrade.jpeg_roundtrip at ``jpeg`` = (quality, subsampling); if None, at the settings a
+    coder.JpegMethod carries (the CLIs' --jpeg-quality / --jpeg-subsampling), else at (50, "420")."""
+    assert method in ("ensemble", "resize", "bitdepth", "jpeg"), f"{method} not in 'ensemble', 'resize'"
     if method == "ensemble":
         return self_ensemble(kern, x)
+    if method == "jpeg":
+        from . import degrade
+        quality, subsampling = jpeg or (getattr(method, "quality", degrade.JPEG_QUALITY),
+                                        getattr(method, "subsampling", degrade.JPEG_SUBSAMPLING))
+        return degrade.jpeg_roundtrip(_dev(x), quality, subsampling)
     if method == "bitdepth":
         return bitdepth_reduction(x, inference=True)
     return random_resize(x, scale=RESIZE_SCALE, random=False)[0]
@@ -242,7 +253,7 @@ def _eval_preprocessed(kern, xs, output_s, clamp):
 
 
 def evaluate_defend(kern, im_adv, im_s, output_s, method="ensemble", clamp=True, adv=False, msssim=True,
-                    profile=None):
+                    profile=None, jpeg=None):
     """self_ensemble.eval with args.defend (self_ensemble.py:173-252), per image.  Returns a list of dicts
     {bpp, mse_in, mse_out, vi, vi_msim[, mse_pre, vi_pre][, best_idx][, nclamped]} and the defended outputs.
     method 'range' (profile: a latent_range.RangeProfile) is attack_rd.py's defended eval: nothing preprocesses
@@ -261,7 +272,7 @@ def evaluate_defend(kern, im_adv, im_s, output_s, method="ensemble", clamp=True,
             for b in range(B):
                 extra[b]["best_idx"] = best_idx[b]
         else:
-            xp = defend(kern, im_, method)
+            xp = defend(kern, im_, method, jpeg)
             if xp.shape != im_s.shape:
                 raise RuntimeError(f"defend '{method}' changed the image size {tuple(im_s.shape)} -> "
                                    f"{tuple(xp.shape)} (the reference's mse_pre fails the same way)")
@@ -277,7 +288,7 @@ def evaluate_defend(kern, im_adv, im_s, output_s, method="ensemble", clamp=True,
     for b in range(B):
         mi, mo = float(mse_in[b]), float(mse_out[b])
         r = {"bpp": float(bpp[b]), "mse_in": mi, "mse_out": mo, "vi": None, "vi_msim": None, **extra[b]}
-        if method in ("resize", "bitdepth"):
+        if method in ("resize", "bitdepth", "jpeg"):
             r["mse_pre"] = float(mse_pre[b])
             r["vi_pre"] = 10.0 * math.log10(r["mse_pre"] / mi) if mi > 0 and r["mse_pre"] > 0 else None
         if mi > 1e-20 and mo > 1e-20:
@@ -387,6 +398,8 @@ class DefendedAttackLoop(AttackLoop):
     torch's device generator, U(-0.5, 0.5) as the reference draws them."""
 
     def __init__(self, kern, im_s, method="ensemble", noise_fn=None, profile=None, **kw):
+        if method == "jpeg":
+            raise NotImplementedError(JPEG_ADV_REASON)
         if method not in ("ensemble", "resize", "bitdepth", "range"):
             raise ValueError(f"{method} not in 'ensemble', 'resize', 'bitdepth', 'range'")
         if method == "range":
@@ -524,11 +537,18 @@ def batch_attack(args):
         print("==================== DEFENSE SETTINGS ====================")
         print("Defense Method:", args.method)
         print("=========================================================")
+    jpeg = None
+    if args.method == "jpeg":
+        if args.adv:
+            raise NotImplementedError(JPEG_ADV_REASON)
+        from . import degrade
+        degrade.validate_jpeg(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
+        jpeg = (args.jpeg_quality, args.jpeg_subsampling)
     net = coder.load_model(args, training=False).to(args.device)
     for p in net.parameters():
         p.requires_grad_(False)
     kern = net.kernels(net.attack_precision(getattr(args, "precision", None)))
-    pre = args.method in ("resize", "bitdepth")
+    pre = args.method in ("resize", "bitdepth", "jpeg")
     profile = None
     if args.method == "range" and (args.defend or args.adv):
         profile = RangeProfile.load(getattr(args, "range_file", None) or RangeProfile.default_path(args), args.device)
@@ -556,7 +576,7 @@ def batch_attack(args):
                            lr=args.lr_attack, clamp=args.clamp, eval_msssim=False)
         if args.defend:
             r = evaluate_defend(kern, res.im_adv, im_s, res.output_s, args.method, args.clamp,
-                                msssim=min(im_s.shape[2:]) > 160, profile=profile)[0][0]
+                                msssim=min(im_s.shape[2:]) > 160, profile=profile, jpeg=jpeg)[0][0]
             bpp, vi = r["bpp"], r["vi"]
             if pre:
                 vi_pre_ += r["vi_pre"] if r["vi_pre"] is not None else 0.0

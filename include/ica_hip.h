@@ -539,6 +539,31 @@ size_t ica_noise_apply_ws_size(int B, int H, int W);
 int ica_noise_apply(const float* im, const float* noise, float* out, int B, int H, int W, float* noise_power,
                     float* mse_in, float* ws, hipStream_t stream);
 
+/* ---- JPEG round trip (ica_jpeg.hip) -----------------------------------------
+ * The baseline-JPEG transform round trip of DESIGN.md "JPEG round trip" on planar NCHW fp32 tensors [B][3][H][W]
+ * (16-byte aligned): 8-bit levels, JFIF YCbCr, 4:2:0 box mean, per 8x8 block DCT / quantise / dequantise / inverse
+ * DCT, triangle chroma upsampling, RGB levels / 255.  No bitstream.  sub is 420 or 444; H and W are multiples of 16
+ * (420) or 8 (444).  A table pair is 128 floats: the luminance table [64] then the chrominance table [64], row-major
+ * (row = vertical frequency), integer values >= 1 built on the host.  Status: 0, -5 for an unsupported problem or a
+ * missing / misaligned pointer, -7 for an out that overlaps x or ref; nothing is launched then.  ws: scratch of the *_ws_size floats (0 for an unsupported
+ * problem): the partial sums, then the decoded Y, Cb and Cr planes as bytes.  No float atomics, fixed-order
+ * reductions: an image's numbers do not depend on the batch, run to run the same bits.
+ *
+ * ica_jpeg_roundtrip: tabs [B][128], one pair per image.  out is a buffer of its own.  ref (optional, with mse): mse[b] =
+ * mean((out - ref)^2). */
+size_t ica_jpeg_roundtrip_ws_size(int B, int H, int W, int sub);
+int ica_jpeg_roundtrip(const float* x, const float* tabs, int B, int H, int W, int sub, const float* ref, float* out,
+                       float* mse, float* ws, hipStream_t stream);
+/* ica_jpeg_sweep: S <= ica_jpeg_sweep_chunk() candidate table pairs tabs [S][128] shared by all images.  The forward
+ * DCT of a block is computed once per launch; for every image with done[b] == 0: mse[b * ld + s0 + s] =
+ * mean((roundtrip_s(x) - x)^2) (no image is written), then idx[b] = s0 + (first s with mse <= budget) and done[b] = 1
+ * if there is one.  remaining[0] = images still without an answer.  Images with done[b] != 0 cost nothing and keep
+ * their mse row.  The caller zeroes done and sets idx to -1 before the first chunk. */
+int ica_jpeg_sweep_chunk(void);
+size_t ica_jpeg_sweep_ws_size(int B, int H, int W, int sub);
+int ica_jpeg_sweep(const float* x, const float* tabs, int S, int B, int H, int W, int sub, float budget, int s0,
+                   float* mse, long ld, int* idx, int* done, int* remaining, float* ws, hipStream_t stream);
+
 /* ---- perturbation transfer (ica_transfer.hip) -------------------------------
  * The pair loop of transfer_noise.py for N noises x M target images of one size, pair (i, j) at index i * M + j.
  * Status as above: -5 for an unsupported problem (N, M < 1, M > 65535, N > 4 * 65535, N * M >= 2^21, H * W >= 2^29) or a
