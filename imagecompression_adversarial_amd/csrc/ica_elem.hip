@@ -74,12 +74,14 @@ constexpr int ELEM_BLOCKS_PER_IMAGE = 256;
 
 // noise_c = Up(Low(noise,-eps),eps); im_in = Up(Low(im_s + noise_c, 0), 1)
 // -> im_in (nChw4c, ch3 = 0) and partial sums of (im_s - im_in)^2.
+// nstride: floats between the noises of two images, 3 HW for a noise per image and 0 for one noise shared by the
+// batch (the universal perturbation, ica_universal.hip).
 __global__ void attack_prologue_kernel(const float* __restrict__ noise, const float* __restrict__ im_s,
                                        float* __restrict__ im_in4, float* __restrict__ part, long HW, float eps,
-                                       int clamp_in) {
+                                       int clamp_in, long nstride) {
   __shared__ float sh[4];
   const int b = blockIdx.y;
-  const float* nz = noise + (long)b * 3 * HW;
+  const float* nz = noise + (long)b * nstride;
   const float* is = im_s + (long)b * 3 * HW;
   float* o4 = im_in4 + (long)b * 4 * HW;
   float acc = 0.f;
@@ -637,7 +639,18 @@ int ica_reduce_rows(const float* part, float* out, int B, int nblk, float scale,
 int ica_attack_prologue_ex(const float* noise, const float* im_s, float* im_in4, float* part, int B, int H, int W,
                            float eps, int clamp_in, hipStream_t st) {
   ICA_LAUNCH(attack_prologue_kernel, dim3(ELEM_BLOCKS_PER_IMAGE, B), dim3(256), 0, st, noise, im_s, im_in4,
-                     part, (long)H * W, eps, clamp_in);
+                     part, (long)H * W, eps, clamp_in, 3L * H * W);
+  ICA_CHECK_LAUNCH();
+  return 0;
+}
+
+// The prologue of the universal perturbation (ica_universal.hip holds its update): one [1][3][H][W] noise for the
+// whole batch, the same kernel at noise stride 0.
+int ica_universal_prologue(const float* noise, const float* im_s, float* im_in4, float* part, int B, int H, int W,
+                           float eps, hipStream_t st) {
+  if (B < 1 || H < 1 || W < 1) return (int)hipErrorInvalidValue;
+  ICA_LAUNCH(attack_prologue_kernel, dim3(ELEM_BLOCKS_PER_IMAGE, B), dim3(256), 0, st, noise, im_s, im_in4,
+                     part, (long)H * W, eps, 1, 0L);
   ICA_CHECK_LAUNCH();
   return 0;
 }

@@ -294,6 +294,20 @@ int ica_attack_adam_ex(float* noise, const float* im_s, const float* gnet4, cons
                        const float* cheap_grad, float* m, float* v, float* im_in_out, int B, int H, int W, float eps,
                        float thr, float invN, float bc2s, float neg_step, int* branch, const int* gpos, int* census,
                        int clamp_in, hipStream_t stream);
+/* ---- universal perturbation (ica_universal.hip; DESIGN.md §8 "Universal perturbation") ----
+ * One noise [1][3][H][W] (with its m, v) for B images: attack_rd.attack_ with a noise that broadcasts over the batch.
+ * ica_universal_prologue: im_in4[b] = Up(Low(im_s[b] + Up(Low(noise,-eps),eps), 0), 1) and the partial sums of
+ * (im_s - im_in)^2, the ops, block-to-pixel mapping and partial layout of ica_attack_prologue (noise stride 0).
+ * ica_universal_adam: cheap = loss_i[0] > thr for the whole batch (the coupled loop has written the batch mean into
+ * every entry; branch[b], census[b] are written for every b); per noise element g_b = cheap ? -2 fl(gscale (s_b -
+ * ii_b)) : gnet4[b] through image b's [0, 1] pass-through, G = ((g_0 + g_1) + ...) + g_{B-1} in that order, then the
+ * noise bounds' pass-through and ica_attack_adam's Adam on noise / m / v.  gnet4 [B][1][H][W][4] is read on the
+ * expensive branch only; im_in_out (optional) [B][3][H][W] gets every image's im_in.  H * W < 2^27. */
+int ica_universal_prologue(const float* noise, const float* im_s, float* im_in4, float* part, int B, int H, int W,
+                           float eps, hipStream_t stream);
+int ica_universal_adam(float* noise, const float* im_s, const float* gnet4, const float* loss_i, float* m, float* v,
+                       float* im_in_out, int B, int H, int W, float eps, float thr, float gscale, float bc2s,
+                       float neg_step, int* branch, int* census, hipStream_t stream);
 /* Branch compaction: sel[0] = E = #images with loss_i <= thr (the network branch, attack_rd.py:334), sel[1..E] =
  * their indexes in order, gpos[b] = row of image b in the compacted sub-batch (-1: cheap branch, no network).
  * ica_attack_adam / ica_roi_adam read the network gradient of image b from row gpos[b] (gpos null: row b) and,
