@@ -119,8 +119,10 @@ _SIGS = {
     "ica_jpeg_sweep_chunk": [],
     "ica_jpeg_roundtrip_ws_size": [_i, _i, _i, _i],
     "ica_jpeg_roundtrip": [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "ica_jpeg_roundtrip_bwd_ws_size": [_i, _i, _i, _i],
+    "ica_jpeg_roundtrip_bwd": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
     "ica_jpeg_sweep_ws_size": [_i, _i, _i, _i],
-    "ica_jpeg_sweep": [_p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _l, _p, _p, _p, _p, _p],
+    "ica_jpeg_sweep":[_p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _l, _p, _p, _p, _p, _p],
     # perturbation transfer: N noises x M targets (ica_transfer.hip)
     "ica_transfer_apply_ws_size": [_i, _i, _i, _i],
     "ica_transfer_apply": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
@@ -179,7 +181,8 @@ _RESTYPES = {"ica_pack_conv_weight_size": _sz, "ica_pack_conv_weight_bf16_size":
              "ica_gauss_blur_ws_size": _sz, "ica_blur_sweep_ws_size": _sz, "ica_noise_apply_ws_size": _sz,
              "ica_transfer_apply_ws_size": _sz, "ica_transfer_score_ws_size": _sz,
              "ica_requant8_ws_size": _sz, "ica_floor_bits_ws_size": _sz, "ica_latent_distrib_ws_size": _sz,
-             "ica_layer_sums_ws_size": _sz, "ica_jpeg_roundtrip_ws_size": _sz, "ica_jpeg_sweep_ws_size": _sz}
+             "ica_layer_sums_ws_size": _sz, "ica_jpeg_roundtrip_ws_size": _sz, "ica_jpeg_sweep_ws_size": _sz,
+             "ica_jpeg_roundtrip_bwd_ws_size": _sz}
 
 
 

@@ -238,4 +238,7 @@ def config():
                         "of test_commands/jpeg.sh)")
     p.add_argument("--jpeg-subsampling", dest="jpeg_subsampling", type=str, default="420", choices=("420", "444"),
                    help="-degrade jpeg / --defend_m jpeg: chroma subsampling (default 420, cjpeg's)")
+    p.add_argument("--jpeg-surrogate", dest="jpeg_surrogate", type=str, default=None, choices=("ste", "cubic"),
+                   help="self_ensemble --adv --defend_m jpeg: what stands in for the gradient of the round trip's "
+                        "coefficient quantiser, 1 (ste) or 3 r^2 (cubic); no default, without it that attack raises")
     return p

@@ -33,6 +33,7 @@ constexpr int JP_TH = 32;                  // tile height: 16 threads x 2 rows, 
 constexpr int JP_CHUNK = 8;                // candidates per sweep launch (their decoded planes live in the workspace)
 constexpr int JP_MAX_BLOCKS = 1024;
 constexpr int JP_TAB = 128;                // floats per table pair: luminance [64], chrominance [64], row-major
+constexpr int JP_STE = 0, JP_CUBIC = 1;    // the surrogates of the backward (include/ica_hip.h)
 
 // 0.5 cos(k pi / 16); C4 is also sqrt(1 / 8), the scale of the DC row
 constexpr float C1 = 0.49039264020161522f, C2 = 0.46193976625564337f, C3 = 0.41573480615127262f,
@@ -366,6 +367,323 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_colour_kernel(const float* __
   }
 }
 
+// ---- the backward under a surrogate (DESIGN.md "JPEG round trip", "The attack through it") ----------------------
+// Roundings of samples have derivative 1, a clamp passes the gradient iff the rounded value lies in 0 .. 255 (step 1:
+// iff 0 <= x <= 1), the coefficient quantiser has derivative d(r), r = c / q - roundf(c / q): 1 (ste) or 3 r^2
+// (cubic).  Everything else is linear and gets its transpose.  The masks and d are those of the forward's own values:
+// both kernels recompute them with the forward's expressions.
+
+ICA_DEV bool passes255(float v) {   // the inclusive mask of level255, on the rounded value; a NaN does not pass
+  const float r = rintf(v);
+  return r >= 0.f && r <= 255.f;
+}
+
+// sample (y, x) of the triangle-upsampled chroma plane (4:2:0) or of the plane itself, minus 128: chroma_patch's value
+template <bool S420>
+ICA_DEV float chroma_at(const unsigned char* __restrict__ P, int Hc, int Wc, int y, int x) {
+  if (!S420) return (float)P[(size_t)y * Wc + x] - 128.f;
+  const int cy = y >> 1, cx = x >> 1;
+  const int ny = (y & 1) ? min(cy + 1, Hc - 1) : max(cy - 1, 0), nx = (x & 1) ? min(cx + 1, Wc - 1) : max(cx - 1, 0);
+  const unsigned char *near = P + (size_t)cy * Wc, *next = P + (size_t)ny * Wc;
+  const float vn = 3.f * (float)near[cx] + (float)next[cx], vx = 3.f * (float)near[nx] + (float)next[nx];
+  return (3.f * vn + vx) * 0.0625f - 128.f;   // integers below 2^12: exact, as in chroma_patch
+}
+
+// weights with which chroma sample c of n collects the pixels 2 c - 1 .. 2 c + 2 along an axis: the transpose of the
+// triangle filter, the replicated edge folded into the edge pixel
+ICA_DEV void triangle_t(int c, int n, float (&w)[4]) {
+  w[0] = c ? 0.25f : 0.f;
+  w[1] = c ? 0.75f : 1.f;
+  w[2] = c < n - 1 ? 0.75f : 1.f;
+  w[3] = c < n - 1 ? 0.25f : 0.f;
+}
+
+// The transpose of steps 6-7 for one 64 x 32 pixel tile: gY [B][H][W], gC [B][2][Hc][Wc].  A thread takes pixels of
+// the tile and, at 4:2:0, of the one-pixel ring around it: R, G, B as jpeg_colour_kernel computes them, the step-7
+// masks, / 255, the transposed YCbCr -> RGB matrix.  At 4:2:0 the full-size chroma gradients of tile and ring wait in
+// LDS and every chroma sample of the tile then gathers its 4 x 4 pixels in a fixed order: no atomics, and a sample's
+// sum does not depend on which tile forms it.
+template <bool S420>
+__global__ __launch_bounds__(JP_THREADS) void jpeg_colour_bwd_kernel(const float* __restrict__ g_out,
+                                                                     const unsigned char* __restrict__ wsY,
+                                                                     const unsigned char* __restrict__ wsC, int H,
+                                                                     int W, float* __restrict__ gY,
+                                                                     float* __restrict__ gC) {
+  constexpr int RING = S420 ? 1 : 0, LW = JP_TW + 2 * RING, LH = JP_TH + 2 * RING;
+  __shared__ float gc[2][S420 ? LH : 1][S420 ? LW : 1];   // 4:2:0 only
+  const int b = blockIdx.z, tid = threadIdx.x;
+  const int x0 = blockIdx.x * JP_TW, y0 = blockIdx.y * JP_TH;
+  const int Wc = S420 ? W / 2 : W, Hc = S420 ? H / 2 : H;
+  const size_t HW = (size_t)H * W, CHW = (size_t)Hc * Wc;
+  const unsigned char* Pb = wsC + (size_t)b * 2 * CHW;
+  const unsigned char* Pr = Pb + CHW;
+  for (int i = tid; i < LW * LH; i += JP_THREADS) {
+    const int ly = i / LW, lx = i - ly * LW;
+    const int y = y0 - RING + ly, x = x0 - RING + lx;
+    float gcb = 0.f, gcr = 0.f;
+    if (y >= 0 && y < H && x >= 0 && x < W) {
+      const size_t at = (size_t)y * W + x;
+      const float yv = (float)wsY[(size_t)b * HW + at];
+      const float cb = chroma_at<S420>(Pb, Hc, Wc, y, x), cr = chroma_at<S420>(Pr, Hc, Wc, y, x);
+      const float R = fmaf(1.402f, cr, yv);
+      const float G = fmaf(-0.714136f, cr, fmaf(-0.344136f, cb, yv));
+      const float Bl = fmaf(1.772f, cb, yv);
+      const float* g = g_out + (size_t)b * 3 * HW + at;
+      const float gR = passes255(R) ? fdiv_rn(g[0], 255.f) : 0.f;
+      const float gG = passes255(G) ? fdiv_rn(g[HW], 255.f) : 0.f;
+      const float gB = passes255(Bl) ? fdiv_rn(g[2 * HW], 255.f) : 0.f;
+      gcb = fmaf(1.772f, gB, -0.344136f * gG);
+      gcr = fmaf(1.402f, gR, -0.714136f * gG);
+      const bool own = ly >= RING && ly < LH - RING && lx >= RING && lx < LW - RING;
+      if (own) gY[(size_t)b * HW + at] = (gR + gG) + gB;
+      if (!S420) {
+        gC[(size_t)b * 2 * CHW + at] = gcb;
+        gC[((size_t)b * 2 + 1) * CHW + at] = gcr;
+      }
+    }
+    if constexpr (S420) {
+      gc[0][ly][lx] = gcb;
+      gc[1][ly][lx] = gcr;
+    }
+  }
+  if constexpr (S420) {
+    __syncthreads();
+    // chroma sample (cy, cx) of the tile: pixels 2 cy - 1 .. 2 cy + 2, that is LDS rows 2 k .. 2 k + 3 of local row k
+    constexpr int TCW = JP_TW / 2, TCH = JP_TH / 2;
+    for (int i = tid; i < 2 * TCW * TCH; i += JP_THREADS) {
+      const int p = i / (TCW * TCH), k = i - p * (TCW * TCH), ky = k / TCW, kx = k - ky * TCW;
+      const int cy = y0 / 2 + ky, cx = x0 / 2 + kx;
+      if (cy >= Hc || cx >= Wc) continue;
+      float wy[4], wx[4];
+      triangle_t(cy, Hc, wy);
+      triangle_t(cx, Wc, wx);
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float* row = &gc[p][2 * ky + j][2 * kx];
+        const float s = (wx[0] * row[0] + wx[1] * row[1]) + (wx[2] * row[2] + wx[3] * row[3]);
+        acc = fmaf(wy[j], s, acc);
+      }
+      gC[((size_t)b * 2 + p) * CHW + (size_t)cy * Wc + cx] = acc;
+    }
+  }
+}
+
+// The transpose of steps 1-5 for one 64 x 32 pixel tile, laid out as jpeg_blocks_kernel's.  The forward is run again up
+// to the decoded samples: the thread of a 4 x 2 pixel patch keeps the masks of steps 1 and 2 for the epilogue, a
+// column task keeps d(r) of its eight coefficients, a row task the step-4 masks of its eight samples.  The gradient
+// tile then takes the planes' place in LDS: mask, forward rows and columns (the transposes of the inverse rows and
+// columns), x d, inverse columns and rows.  With d = 1 (ste) the orthonormal pair is the identity and is left out.
+template <bool S420, bool CUBIC>
+__global__ __launch_bounds__(JP_THREADS) void jpeg_blocks_bwd_kernel(const float* __restrict__ x,
+                                                                     const float* __restrict__ tabs, int H, int W,
+                                                                     const float* __restrict__ gY,
+                                                                     const float* __restrict__ gC,
+                                                                     float* __restrict__ g_x) {
+  __shared__ __attribute__((aligned(16))) float pl[3][JP_TH][JP_TW];
+  constexpr int NR = S420 ? 2 : 3;
+  const int b = blockIdx.z, tid = threadIdx.x;
+  const int x0 = blockIdx.x * JP_TW, y0 = blockIdx.y * JP_TH;
+  const size_t HW = (size_t)H * W;
+  const int tx = tid & 15, ty = tid >> 4;
+  const int px = x0 + 4 * tx, py = y0 + 2 * ty;
+  const bool in = px < W && py < H;          // whole MCUs: a 4 x 2 patch is inside the image or outside it
+  // bit 8 ch + 4 r + e: step 1 passes channel ch of pixel (r, e); step 2 passes plane ch (Y, Cb, Cr) there
+  unsigned m1 = 0u, m2 = 0u;
+
+  {  // steps 1-3, as jpeg_blocks_kernel
+    float cb[2][4], cr[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      f32x4 c[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)
+        c[ch] = in ? ld4(x + ((size_t)b * 3 + ch) * HW + (size_t)(py + r) * W + px) : f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 yv;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+          if (c[ch][e] >= 0.f && c[ch][e] <= 1.f) m1 |= 1u << (8 * ch + 4 * r + e);
+        const float R = rintf(fmul_rn(clamp01(c[0][e]), 255.f)), G = rintf(fmul_rn(clamp01(c[1][e]), 255.f)),
+                    Bl = rintf(fmul_rn(clamp01(c[2][e]), 255.f));
+        const float fy = fmaf(0.114f, Bl, fmaf(0.587f, G, 0.299f * R));
+        const float fb = fmaf(0.5f, Bl, fmaf(-0.331264f, G, fmaf(-0.168736f, R, 128.f)));
+        const float fr = fmaf(-0.081312f, Bl, fmaf(-0.418688f, G, fmaf(0.5f, R, 128.f)));
+        if (passes255(fy)) m2 |= 1u << (4 * r + e);
+        if (passes255(fb)) m2 |= 1u << (8 + 4 * r + e);
+        if (passes255(fr)) m2 |= 1u << (16 + 4 * r + e);
+        yv[e] = level255(fy);
+        cb[r][e] = level255(fb);
+        cr[r][e] = level255(fr);
+      }
+      st4(&pl[0][2 * ty + r][4 * tx], yv);
+      if (!S420) {
+        st4(&pl[1][2 * ty + r][4 * tx], f32x4{cb[r][0], cb[r][1], cb[r][2], cb[r][3]});
+        st4(&pl[2][2 * ty + r][4 * tx], f32x4{cr[r][0], cr[r][1], cr[r][2], cr[r][3]});
+      }
+    }
+    if (S420) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        pl[1][ty][2 * tx + h] = 0.25f * ((cb[0][2 * h] + cb[0][2 * h + 1]) + (cb[1][2 * h] + cb[1][2 * h + 1]));
+        pl[2][ty][2 * tx + h] = 0.25f * ((cr[0][2 * h] + cr[0][2 * h + 1]) + (cr[1][2 * h] + cr[1][2 * h + 1]));
+      }
+    }
+  }
+  __syncthreads();
+
+  // forward rows
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    int p, k;
+    if (!task_of<S420>(i, tid, p, k)) continue;
+    const int nbx = plane_nbx<S420>(p), y = k / nbx, bx = k - y * nbx;
+    float* row = &pl[p][y][8 * bx];
+    const f32x4 lo = ld4(row), hi = ld4(row + 4);
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[e] = lo[e] - 128.f;
+      v[4 + e] = hi[e] - 128.f;
+    }
+    dct8(v);
+    st4(row, f32x4{v[0], v[1], v[2], v[3]});
+    st4(row + 4, f32x4{v[4], v[5], v[6], v[7]});
+  }
+  __syncthreads();
+
+  // forward columns, quantise (d(r) stays with the column task), dequantise, inverse columns
+  float dq[CUBIC ? NR : 1][8];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    int p, k;
+    if (!task_of<S420>(i, tid, p, k)) continue;
+    const int w = 8 * plane_nbx<S420>(p), by = k / w, xx = k - by * w;
+    const float* tq = tabs + (size_t)b * JP_TAB + (p ? 64 : 0) + (xx & 7);
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = pl[p][8 * by + u][xx];
+    dct8(v);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const float q = tq[8 * u], t = fdiv_rn(v[u], q), n = roundf(t);
+      if constexpr (CUBIC) {
+        const float r = fsub_rn(t, n);
+        dq[i][u] = 3.f * fmul_rn(r, r);
+      }
+      v[u] = fmul_rn(n, q);
+    }
+    idct8(v);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) pl[p][8 * by + u][xx] = v[u];
+  }
+  __syncthreads();
+
+  // inverse rows give the decoded samples and so the step-4 masks; the row task then puts the masked gradient of its
+  // eight samples in their place (it alone touches them between two barriers), with cubic after the forward row pass
+  const int Wc = S420 ? W / 2 : W, Hc = S420 ? H / 2 : H;
+  const int cx0 = S420 ? x0 / 2 : x0, cy0 = S420 ? y0 / 2 : y0;
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    int p, k;
+    if (!task_of<S420>(i, tid, p, k)) continue;
+    const int nbx = plane_nbx<S420>(p), y = k / nbx, bx = k - y * nbx;
+    float* row = &pl[p][y][8 * bx];
+    const f32x4 lo = ld4(row), hi = ld4(row + 4);
+    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    idct8(v);
+    const float* src;
+    bool have;
+    if (p == 0) {
+      const int gx = x0 + 8 * bx, gy = y0 + y;
+      have = gx < W && gy < H;
+      src = gY + (size_t)b * HW + (size_t)gy * W + gx;
+    } else {
+      const int gx = cx0 + 8 * bx, gy = cy0 + y;
+      have = gx < Wc && gy < Hc;
+      src = gC + ((size_t)b * 2 + (p - 1)) * ((size_t)Hc * Wc) + (size_t)gy * Wc + gx;
+    }
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 glo = have ? ld4(src) : z, ghi = have ? ld4(src + 4) : z;
+    float g[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      g[e] = passes255(v[e] + 128.f) ? glo[e] : 0.f;
+      g[4 + e] = passes255(v[4 + e] + 128.f) ? ghi[e] : 0.f;
+    }
+    if constexpr (CUBIC) dct8(g);
+    st4(row, f32x4{g[0], g[1], g[2], g[3]});
+    st4(row + 4, f32x4{g[4], g[5], g[6], g[7]});
+  }
+  __syncthreads();
+
+  if constexpr (CUBIC) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      int p, k;
+      if (!task_of<S420>(i, tid, p, k)) continue;
+      const int w = 8 * plane_nbx<S420>(p), by = k / w, xx = k - by * w;
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = pl[p][8 * by + u][xx];
+      dct8(v);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = fmul_rn(v[u], dq[i][u]);
+      idct8(v);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) pl[p][8 * by + u][xx] = v[u];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      int p, k;
+      if (!task_of<S420>(i, tid, p, k)) continue;
+      const int nbx = plane_nbx<S420>(p), y = k / nbx, bx = k - y * nbx;
+      float* row = &pl[p][y][8 * bx];
+      const f32x4 lo = ld4(row), hi = ld4(row + 4);
+      float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      idct8(v);
+      st4(row, f32x4{v[0], v[1], v[2], v[3]});
+      st4(row + 4, f32x4{v[4], v[5], v[6], v[7]});
+    }
+    __syncthreads();
+  }
+
+  // epilogue, the patch of the prologue: box-mean transpose, step-2 masks, transposed RGB -> YCbCr, x 255, step-1 mask
+  if (!in) return;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const f32x4 ly = ld4(&pl[0][2 * ty + r][4 * tx]);
+    f32x4 lb, lr;
+    if (S420) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        lb[e] = 0.25f * pl[1][ty][2 * tx + (e >> 1)];
+        lr[e] = 0.25f * pl[2][ty][2 * tx + (e >> 1)];
+      }
+    } else {
+      lb = ld4(&pl[1][2 * ty + r][4 * tx]);
+      lr = ld4(&pl[2][2 * ty + r][4 * tx]);
+    }
+    f32x4 o[3];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int bit = 4 * r + e;
+      const float a = (m2 >> bit) & 1u ? ly[e] : 0.f, c = (m2 >> (8 + bit)) & 1u ? lb[e] : 0.f,
+                  d = (m2 >> (16 + bit)) & 1u ? lr[e] : 0.f;
+      const float gR = fmaf(0.5f, d, fmaf(-0.168736f, c, 0.299f * a));
+      const float gG = fmaf(-0.418688f, d, fmaf(-0.331264f, c, 0.587f * a));
+      const float gB = fmaf(-0.081312f, d, fmaf(0.5f, c, 0.114f * a));
+      o[0][e] = (m1 >> bit) & 1u ? fmul_rn(gR, 255.f) : 0.f;
+      o[1][e] = (m1 >> (8 + bit)) & 1u ? fmul_rn(gG, 255.f) : 0.f;
+      o[2][e] = (m1 >> (16 + bit)) & 1u ? fmul_rn(gB, 255.f) : 0.f;
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) st4(g_x + ((size_t)b * 3 + ch) * HW + (size_t)(py + r) * W + px, o[ch]);
+  }
+}
+
 // 0 if (B, H, W, sub) is a supported problem: sub is 420 or 444, H and W multiples of the MCU (16 or 8)
 int jpeg_check(int B, int H, int W, int sub) {
   if (sub != 420 && sub != 444) return -5;
@@ -429,6 +747,46 @@ int ica_jpeg_roundtrip(const float* x, const float* tabs, int B, int H, int W, i
     finish_rows(st, ws, B, jpeg_blocks(H, W), (float)((long)3 * H * W), mse);
     ICA_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+// workspace of the backward, in floats: gY [B][H][W], gC [B][2][Hc][Wc], then the decoded byte planes
+size_t ica_jpeg_roundtrip_bwd_ws_size(int B, int H, int W, int sub) {
+  if (jpeg_check(B, H, W, sub)) return 0;
+  return (size_t)B * H * W * (sub == 420 ? 3 : 6) / 2 + (size_t)B * jpeg_plane_bytes(H, W, sub) / 4;
+}
+
+int ica_jpeg_roundtrip_bwd(const float* x, const float* tabs, const float* g_out, int B, int H, int W, int sub,
+                           int surrogate, float* g_x, float* ws, hipStream_t st) {
+  const int rc = jpeg_check(B, H, W, sub);
+  if (rc) return rc;
+  if (surrogate != JP_STE && surrogate != JP_CUBIC) return -5;
+  if (!x || !tabs || !g_out || !g_x || !ws) return -5;
+  if (!aligned16(x) || !aligned16(g_out) || !aligned16(g_x) || !aligned16(ws)) return -5;
+  const size_t bytes = (size_t)B * 3 * H * W * sizeof(float);
+  if (overlaps(x, bytes, g_x, bytes) || overlaps(g_out, bytes, g_x, bytes)) return -7;
+  const size_t HW = (size_t)H * W, CHW = sub == 420 ? HW / 4 : HW;
+  float* gY = ws;
+  float* gC = gY + (size_t)B * HW;
+  unsigned char* wsY = reinterpret_cast<unsigned char*>(gC + (size_t)B * 2 * CHW);
+  unsigned char* wsC = wsY + (size_t)B * HW;
+  const dim3 tiles((W + JP_TW - 1) / JP_TW, (H + JP_TH - 1) / JP_TH, B), threads(JP_THREADS);
+  const int* none = nullptr;
+#define JPEG_BWD(S420, CUBIC)                                                                                    \
+  ICA_LAUNCH((jpeg_blocks_kernel<S420, false>), tiles, threads, 0, st, x, tabs, 1, H, W, none, wsY, wsC);          \
+  ICA_CHECK_LAUNCH();                                                                                             \
+  ICA_LAUNCH((jpeg_colour_bwd_kernel<S420>), tiles, threads, 0, st, g_out, (const unsigned char*)wsY,              \
+             (const unsigned char*)wsC, H, W, gY, gC);                                                            \
+  ICA_CHECK_LAUNCH();                                                                                             \
+  ICA_LAUNCH((jpeg_blocks_bwd_kernel<S420, CUBIC>), tiles, threads, 0, st, x, tabs, H, W, (const float*)gY,        \
+             (const float*)gC, g_x);                                                                              \
+  ICA_CHECK_LAUNCH()
+  if (sub == 420) {
+    if (surrogate == JP_CUBIC) { JPEG_BWD(true, true); } else { JPEG_BWD(true, false); }
+  } else {
+    if (surrogate == JP_CUBIC) { JPEG_BWD(false, true); } else { JPEG_BWD(false, false); }
+  }
+#undef JPEG_BWD
   return 0;
 }
 

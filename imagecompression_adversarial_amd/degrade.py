@@ -11,6 +11,7 @@ evaluate_deblur   test_deblur (random_noise.py:20-48), per image
 jpeg_tables       the T.81 Annex K tables scaled by the IJG rule, as integers on the host
 jpeg_roundtrip    the baseline-JPEG transform round trip (ica_jpeg.hip; DESIGN.md "JPEG round trip"): what
                   test_commands/jpeg.sh makes with ``cjpeg -q 50``, and the input-transformation defence
+jpeg_roundtrip_bwd its input gradient under a surrogate ("ste" or "cubic"): the attack through the JPEG defence
 jpeg_to_budget    the first quality from 1 upward whose round trip fits the MSE budget
 evaluate_jpeg     test's numbers with the JPEG error in the place of the noise
 
@@ -98,14 +99,18 @@ JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99,
                47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
 JPEG_QUALITY, JPEG_SUBSAMPLING = 50, "420"     # test_commands/jpeg.sh: cjpeg -q 50, cjpeg's default subsampling
 JPEG_MCU = {"420": 16, "444": 8}
+JPEG_SURROGATES = ("ste", "cubic")             # ICA_JPEG_STE, ICA_JPEG_CUBIC: the index is the C value
 
 
 def validate_jpeg(H=None, W=None, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING, noise=None,
-                  factor=SWEEP_FACTOR):
-    """ValueError unless ica_jpeg_roundtrip / ica_jpeg_sweep take this problem (include/ica_hip.h).  ``quality``: one
-    value or a list; H, W None checks the flags alone."""
+                  factor=SWEEP_FACTOR, surrogate=None):
+    """ValueError unless ica_jpeg_roundtrip / ica_jpeg_sweep / ica_jpeg_roundtrip_bwd take this problem
+    (include/ica_hip.h).  ``quality``: one value or a list; H, W None checks the flags alone; ``surrogate`` None:
+    not a backward."""
     if subsampling not in JPEG_MCU:
         raise ValueError(f"subsampling {subsampling!r} is not one of {sorted(JPEG_MCU)}")
+    if surrogate is not None and surrogate not in JPEG_SURROGATES:
+        raise ValueError(f"surrogate {surrogate!r} is not one of {list(JPEG_SURROGATES)}")
     for q in (quality if isinstance(quality, (tuple, list)) else [quality]):
         if isinstance(q, bool) or not isinstance(q, int) or q < 1 or q > 100:
             raise ValueError(f"a JPEG quality is an integer in 1 .. 100, got {q!r}")
@@ -160,6 +165,29 @@ def jpeg_roundtrip(x, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING, ref=No
     ws = _jpeg_ws("ica_jpeg_roundtrip_ws_size", B, H, W, sub, x.device)
     call("ica_jpeg_roundtrip", ptr(x), ptr(tabs), B, H, W, sub, ptr(ref), ptr(out), ptr(mse), ptr(ws), stream())
     return out if ref is None else (out, mse)
+
+
+def jpeg_roundtrip_bwd(x, g, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING, surrogate=None):
+    """g_x: the gradient with respect to x of sum(g * jpeg_roundtrip(x, quality, subsampling)) under ``surrogate``
+    (DESIGN.md "JPEG round trip", "The attack through it"): "ste", the quantiser has derivative 1, or "cubic",
+    3 r^2 with r the coefficient's distance to its rounded value in steps.  No default: the caller names it."""
+    B, H, W = K.check_image(x, "x")
+    qs = list(quality) if isinstance(quality, (tuple, list)) else [quality] * B
+    if surrogate is None:
+        raise ValueError(f"name the surrogate: one of {list(JPEG_SURROGATES)}")
+    validate_jpeg(H, W, qs, subsampling, surrogate=surrogate)
+    if len(qs) != B:
+        raise ValueError(f"{len(qs)} qualities for a batch of {B}")
+    if g.shape != x.shape:
+        raise ValueError(f"g {tuple(g.shape)} differs from x {tuple(x.shape)}")
+    K._dev_check(g, "g")
+    sub = int(subsampling)
+    tabs = _jpeg_tabs(tuple(qs), str(x.device))
+    gx = torch.empty_like(x)
+    ws = _jpeg_ws("ica_jpeg_roundtrip_bwd_ws_size", B, H, W, sub, x.device)
+    call("ica_jpeg_roundtrip_bwd", ptr(x), ptr(tabs), ptr(g), B, H, W, sub, JPEG_SURROGATES.index(surrogate), ptr(gx),
+         ptr(ws), stream())
+    return gx
 
 
 def jpeg_sweep(x, noise, factor=SWEEP_FACTOR, subsampling=JPEG_SUBSAMPLING):

@@ -12,6 +12,9 @@ defend              self_ensemble.py:156-171
 evaluate_defend     self_ensemble.py:173-252 (eval with args.defend)
 attack_/main        self_ensemble.py:275-444 (the L2 attack loop == attack.attack_batch, then eval with defend)
 DefendedAttackLoop  self_ensemble.py:253-326 with --adv: the attack through defend() (ensemble / bitdepth / resize)
+jpeg (extension)    --defend_m jpeg: degrade.jpeg_roundtrip as a pre-processing defence; with --adv the attack through
+                    it needs --jpeg-surrogate ste|cubic, the stated stand-in for the gradient the roundings lack
+                    (degrade.jpeg_roundtrip_bwd; DESIGN.md "JPEG round trip", "The attack through it")
 range (extension)   --defend_m range: the latent-range clamp of attack_rd.py:263-268 (clamp_value_naive) as a fourth
                     defence of this eval, and the attack through it (latent_range.py, ica_latent.hip); the
                     profile comes from --range-file (default: the reference's ./attack/data/..._range.pt)
@@ -199,8 +202,16 @@ def self_ensemble(kern, x):
     return best_mse, best_x, best_idx
 
 
-JPEG_ADV_REASON = ("the attack through the JPEG defence is not built: the round trip's roundings have no gradient, and "
-                   "a straight-through variant is a separate piece of work")
+JPEG_ADV_REASON = ("the attack through the JPEG defence needs a surrogate: the round trip's roundings have no gradient, "
+                   "and which stand-in takes its place is the caller's choice (surrogate='ste' or 'cubic', "
+                   "--jpeg-surrogate on the command line)")
+
+
+def _jpeg_settings(method, jpeg):
+    """(quality, subsampling): ``jpeg`` itself, else what a coder.JpegMethod carries, else (50, "420")."""
+    from . import degrade
+    return jpeg or (getattr(method, "quality", degrade.JPEG_QUALITY),
+                    getattr(method, "subsampling", degrade.JPEG_SUBSAMPLING))
 
 
 def defend(kern, x, method="ensemble", jpeg=None):
@@ -212,8 +223,7 @@ def defend(kern, x, method="ensemble", jpeg=None):
         return self_ensemble(kern, x)
     if method == "jpeg":
         from . import degrade
-        quality, subsampling = jpeg or (getattr(method, "quality", degrade.JPEG_QUALITY),
-                                        getattr(method, "subsampling", degrade.JPEG_SUBSAMPLING))
+        quality, subsampling = _jpeg_settings(method, jpeg)
         return degrade.jpeg_roundtrip(_dev(x), quality, subsampling)
     if method == "bitdepth":
         return bitdepth_reduction(x, inference=True)
@@ -390,6 +400,9 @@ class DefendedAttackLoop(AttackLoop):
                  for every model), the usual bounded L2 output loss.
       resize   : x_ = up(down(x)) (antialiased bicubic 243/256), x_hat = g_s(g_a(x_) + u_y); gradient through the
                  transposed resample passes.
+      jpeg     : (an extension) x_ = jpeg_roundtrip(x) at ``jpeg`` = (quality, subsampling), x_hat = g_s(g_a(x_) + u_y);
+                 the round trip has no gradient, so the backward is degrade.jpeg_roundtrip_bwd under ``surrogate``
+                 ("ste" or "cubic"; None raises: the choice is the caller's).
       range    : (no such loop in the reference; in the spirit of its --adv) x_hat = g_s(clamp(g_a(im_in))) on the
                  unquantised latent, attack_our with clamp_value_naive between the transforms; the gradient goes
                  g_s backward -> the clamp's where-masks (ica_latent_clamp_bwd) -> g_a backward.  No noise draw:
@@ -397,11 +410,16 @@ class DefendedAttackLoop(AttackLoop):
     noise_fn(step, name, shape) may supply the uniform draws ("x": bit-depth noise, "y": latent noise); default:
     torch's device generator, U(-0.5, 0.5) as the reference draws them."""
 
-    def __init__(self, kern, im_s, method="ensemble", noise_fn=None, profile=None, **kw):
+    def __init__(self, kern, im_s, method="ensemble", noise_fn=None, profile=None, jpeg=None, surrogate=None, **kw):
         if method == "jpeg":
-            raise NotImplementedError(JPEG_ADV_REASON)
-        if method not in ("ensemble", "resize", "bitdepth", "range"):
-            raise ValueError(f"{method} not in 'ensemble', 'resize', 'bitdepth', 'range'")
+            if surrogate is None:
+                raise NotImplementedError(JPEG_ADV_REASON)
+            from . import degrade
+            self.jpeg = _jpeg_settings(method, jpeg)
+            degrade.validate_jpeg(quality=self.jpeg[0], subsampling=self.jpeg[1], surrogate=surrogate)
+            self.surrogate = surrogate
+        elif method not in ("ensemble", "resize", "bitdepth", "range"):
+            raise ValueError(f"{method} not in 'ensemble', 'resize', 'bitdepth', 'range', 'jpeg'")
         if method == "range":
             if getattr(kern, "precision", "fp32") == "bf16":
                 raise NotImplementedError("the attack through the latent clamp runs fp32 / x6 operands, not bf16")
@@ -451,6 +469,9 @@ class DefendedAttackLoop(AttackLoop):
             u = self._uniform("x", x.shape, self._i)
             xp = torch.empty_like(x)
             call("ica_bitdepth_noise", ptr(x), ptr(u), ptr(xp), x.numel(), BITDEPTH_SCALE, stream())
+        elif self.method == "jpeg":
+            from . import degrade
+            xp = degrade.jpeg_roundtrip(x, *self.jpeg)
         else:
             xp = self.resize.forward(x)
         y4, sa = kern.g_a(K.to_nc4(xp), save=True)
@@ -465,6 +486,8 @@ class DefendedAttackLoop(AttackLoop):
         if self.method == "bitdepth":
             gx = torch.empty_like(g)
             call("ica_bitdepth_noise_bwd", ptr(g), ptr(gx), g.numel(), BITDEPTH_SCALE, stream())
+        elif self.method == "jpeg":
+            gx = degrade.jpeg_roundtrip_bwd(x, g, *self.jpeg, surrogate=self.surrogate)
         else:
             gx = self.resize.backward(g)
         return K.to_nc4(gx)
@@ -505,15 +528,17 @@ class DefendedAttackLoop(AttackLoop):
 
 
 def adv_attack_batch(kern, im_s, method="ensemble", steps=1001, epsilon=16.0, noise_thr=1e-4, lr=0.01, clamp=True,
-                     noise_fn=None, defend_eval=False, eval_msssim=True, record=False, profile=None):
+                     noise_fn=None, defend_eval=False, eval_msssim=True, record=False, profile=None, jpeg=None,
+                     surrogate=None):
     """self_ensemble.attack_ with --adv (per image), then its eval (with --defend when defend_eval).
+    jpeg, surrogate: the settings of method 'jpeg' (DefendedAttackLoop).
     Returns (AttackResult-like dict of the eval, the loop)."""
-    loop = DefendedAttackLoop(kern, im_s, method, noise_fn, profile, steps=steps, epsilon=epsilon,
-                              noise_thr=noise_thr, lr=lr, clamp=clamp)
+    loop = DefendedAttackLoop(kern, im_s, method, noise_fn, profile, jpeg=jpeg, surrogate=surrogate, steps=steps,
+                              epsilon=epsilon, noise_thr=noise_thr, lr=lr, clamp=clamp)
     branches = loop.run(record=record)
     if defend_eval:
         res, out = evaluate_defend(kern, loop.im_in, loop.im_s, loop.output_s, method, clamp, adv=True,
-                                   msssim=eval_msssim, profile=profile)
+                                   msssim=eval_msssim, profile=profile, jpeg=jpeg)
     else:
         im_, out, bpp, mse_in, mse_out, msim_in, msim_out, vi, vi_msim = evaluate(
             kern, loop.im_in, loop.im_s, loop.output_s, clamp, adv=True, msssim=eval_msssim)
@@ -539,10 +564,11 @@ def batch_attack(args):
         print("=========================================================")
     jpeg = None
     if args.method == "jpeg":
-        if args.adv:
+        if args.adv and args.jpeg_surrogate is None:
             raise NotImplementedError(JPEG_ADV_REASON)
         from . import degrade
-        degrade.validate_jpeg(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling)
+        degrade.validate_jpeg(quality=args.jpeg_quality, subsampling=args.jpeg_subsampling,
+                              surrogate=args.jpeg_surrogate)
         jpeg = (args.jpeg_quality, args.jpeg_subsampling)
     net = coder.load_model(args, training=False).to(args.device)
     for p in net.parameters():
@@ -560,7 +586,7 @@ def batch_attack(args):
             rs, _, loop, _ = adv_attack_batch(kern, im_s, args.method, steps=args.steps, epsilon=args.epsilon,
                                               noise_thr=args.noise, lr=args.lr_attack, clamp=args.clamp,
                                               defend_eval=args.defend, eval_msssim=min(im_s.shape[2:]) > 160,
-                                              profile=profile)
+                                              profile=profile, jpeg=jpeg, surrogate=args.jpeg_surrogate)
             r = rs[0]
             bpp, vi = r["bpp"], r["vi"]
             if args.defend and pre:
@@ -598,7 +624,8 @@ def batch_attack(args):
 
 
 def config():
-    """coder.config() plus this CLI's own flag (the way the reference's transfer_noise.py extends the parser)."""
+    """coder.config() plus this CLI's own flag (the way the reference's transfer_noise.py extends the parser).
+    --jpeg-surrogate comes with coder.config()'s other --jpeg-* flags."""
     p = coder.config()
     p.add_argument("--range-file", dest="range_file", type=str, default=None,
                    help="--defend_m range: the latent-range profile ([channel_max, channel_min], feature_range's "

@@ -568,6 +568,20 @@ int ica_noise_apply(const float* im, const float* noise, float* out, int B, int 
 size_t ica_jpeg_roundtrip_ws_size(int B, int H, int W, int sub);
 int ica_jpeg_roundtrip(const float* x, const float* tabs, int B, int H, int W, int sub, const float* ref, float* out,
                        float* mse, float* ws, hipStream_t stream);
+/* ica_jpeg_roundtrip_bwd: g_x = the vector-Jacobian product of the round trip at x with g_out, under a surrogate
+ * (DESIGN.md "JPEG round trip", "The attack through it"): a sample rounding has derivative 1, a clamp passes the
+ * gradient iff the rounded value lies in 0 .. 255 (step 1: iff 0 <= x <= 1), the coefficient quantiser q roundf(c / q)
+ * has derivative 1 (ICA_JPEG_STE) or 3 r^2, r = c / q - roundf(c / q) (ICA_JPEG_CUBIC); everything else is transposed.
+ * Stateless: it runs the forward's block pass into ws (ica_jpeg_roundtrip_bwd_ws_size floats: the fp32 gradient
+ * planes gY [B][H][W] and gC [B][2][Hc][Wc], then the decoded byte planes) and takes the masks and r from the
+ * forward's own values.  x, tabs, B, H, W, sub as for ica_jpeg_roundtrip; g_out and g_x [B][3][H][W], 16-byte
+ * aligned.  -5: unsupported shape, null or misaligned pointer, unknown surrogate; -7: g_x overlaps x or g_out.  No
+ * atomics: an image's gradient does not depend on the batch or the tiling, run to run the same bits. */
+#define ICA_JPEG_STE 0
+#define ICA_JPEG_CUBIC 1
+size_t ica_jpeg_roundtrip_bwd_ws_size(int B, int H, int W, int sub);
+int ica_jpeg_roundtrip_bwd(const float* x, const float* tabs, const float* g_out, int B, int H, int W, int sub,
+                           int surrogate, float* g_x, float* ws, hipStream_t stream);
 /* ica_jpeg_sweep: S <= ica_jpeg_sweep_chunk() candidate table pairs tabs [S][128] shared by all images.  The forward
  * DCT of a block is computed once per launch; for every image with done[b] == 0: mse[b * ld + s0 + s] =
  * mean((roundtrip_s(x) - x)^2) (no image is written), then idx[b] = s0 + (first s with mse <= budget) and done[b] = 1

@@ -1,4 +1,4 @@
-"""Times ica_jpeg_roundtrip and one chunk of ica_jpeg_sweep on B x 3 x H x W (default 32 x 768 x 512, Kodak's size) with
+"""Times ica_jpeg_roundtrip, ica_jpeg_roundtrip_bwd (both surrogates) and one chunk of ica_jpeg_sweep on B x 3 x H x W (default 32 x 768 x 512, Kodak's size) with
 device events around ``--reps`` back-to-back calls (default 5000: a timed window of about half a second for the round
 trip, two for the sweep chunk) after a warm-up, and prints one JSON line.
 
@@ -6,7 +6,10 @@ trip, two for the sweep chunk) after a warm-up, and prints one JSON line.
 
 traffic_bytes is what the two passes of a call move by construction (DESIGN.md "JPEG round trip"): the fp32 image in
 and out, the fused MSE's read of ref, and the byte planes written once and read once; gbps = traffic / time.  The
-sweep chunk reads x twice (once per pass) and moves the byte planes of its 8 candidates.
+sweep chunk reads x twice (once per pass) and moves the byte planes of its 8 candidates.  The backward is three
+passes: the forward's block pass (x in, byte planes out), the colour transpose (g and the byte planes in, the fp32
+gradient planes out: 4 B/px of Y and 2 B/px (4:2:0) or 8 B/px (4:4:4) of chroma) and the block transpose (x and the
+gradient planes in, g_x out).
 """
 import argparse
 import json
@@ -62,6 +65,14 @@ def main():
                                stream()), args.reps)
         traffic = px * (12 + 12 + 12 + 2 * plane)
         out["roundtrip_mse_" + sub] = {"ms": t * 1e3, "traffic_bytes": traffic, "gbps": traffic / t / 1e9}
+        gout, gx = torch.randn(x.shape, generator=g).to(dev), torch.empty_like(x)
+        wsb = torch.empty(lib().ica_jpeg_roundtrip_bwd_ws_size(B, H, W, s), device=dev)
+        gplanes = 4 + (2 if sub == "420" else 8)
+        traffic = px * ((12 + plane) + (12 + plane + gplanes) + (12 + gplanes + 12))
+        for k, name in enumerate(degrade.JPEG_SURROGATES):
+            t = timed(lambda: call("ica_jpeg_roundtrip_bwd", ptr(x), ptr(tabs), ptr(gout), B, H, W, s, k, ptr(gx),
+                                   ptr(wsb), stream()), args.reps)
+            out[f"bwd_{name}_{sub}"] = {"ms": t * 1e3, "traffic_bytes": traffic, "gbps": traffic / t / 1e9}
         S = lib().ica_jpeg_sweep_chunk()
         all_tabs = degrade._jpeg_tabs(tuple(range(1, 101)), str(dev))
         msew = torch.empty((B, 100), device=dev)
