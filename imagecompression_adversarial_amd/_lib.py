@@ -128,6 +128,15 @@ _SIGS = {
     "ica_transfer_apply": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "ica_transfer_score_ws_size": [_i, _i, _i, _i],
     "ica_transfer_score": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
+    # frequency bands of a perturbation: study and band-limited attack step (ica_band.hip)
+    "ica_band_split_chunk": [],
+    "ica_band_max_variants": [],
+    "ica_band_split_ws_size": [_i, _i, _i, _i],
+    "ica_band_split": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "ica_band_project": [_p, _i, _i, _i, _i, _p, _p],
+    "ica_band_prologue_ws_size": [_i, _i, _i],
+    "ica_band_prologue": [_p, _p, _p, _p, _i, _i, _i, _f, _i, _p, _p],
+    "ica_band_adam": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _i, _p],
     # iterated re-compression: the step between two generations (ica_recompress.hip)
     "ica_requant8_ws_size": [_i, _i, _i],
     "ica_requant8": [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
@@ -182,7 +191,8 @@ _RESTYPES = {"ica_pack_conv_weight_size": _sz, "ica_pack_conv_weight_bf16_size":
              "ica_transfer_apply_ws_size": _sz, "ica_transfer_score_ws_size": _sz,
              "ica_requant8_ws_size": _sz, "ica_floor_bits_ws_size": _sz, "ica_latent_distrib_ws_size": _sz,
              "ica_layer_sums_ws_size": _sz, "ica_jpeg_roundtrip_ws_size": _sz, "ica_jpeg_sweep_ws_size": _sz,
-             "ica_jpeg_roundtrip_bwd_ws_size": _sz}
+             "ica_jpeg_roundtrip_bwd_ws_size": _sz, "ica_band_split_ws_size": _sz,
+             "ica_band_prologue_ws_size": _sz}
 
 
 

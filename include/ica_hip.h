@@ -611,6 +611,43 @@ size_t ica_transfer_score_ws_size(int N, int M, int H, int W);
 int ica_transfer_score(const float* x_hat4, const float* x_s4, int N, int M, int H, int W, int clamp, float* mse_out,
                        float* ws, hipStream_t stream);
 
+/* ---- frequency bands of a perturbation (ica_band.hip; DESIGN.md "Band VI") ----
+ * The orthonormal 8x8 block DCT-II of every channel plane, blocks aligned to the image origin, fp32, rows then columns
+ * (the transform pair of the JPEG round trip).  Coefficient (u, v) belongs to band max(u, v) = 0..7; a band set is a
+ * mask 0..255, bit k selecting band k; P_S = IDCT . [band in S] . DCT.  Images are planar NCHW fp32 [B][3][H][W].
+ * Status as above: -5 for an unsupported problem (H or W not a positive multiple of 8, B < 1, B > 65535,
+ * H * W >= 2^29, V < 1, V > ica_band_max_variants(), a mask outside 0..255) or a missing / misaligned pointer, -7 for
+ * an output that overlaps an input or another output; nothing is launched then.  ws: scratch of the *_ws_size floats
+ * (0 for an unsupported problem).  Reductions are fixed-order and an image's blocks depend on (H, W) only: a row's
+ * numbers are the same bits alone and in a batch, run to run.
+ *
+ * ica_band_split: n = im_adv - im_s.  energy [B][8]: energy[b][k] = |P_{k} n[b]|^2 / (3 H W), summed over the
+ * coefficients.  With out: for the V masks (a host array, read before the call returns) out[v * B + b] =
+ * clamp(im_s[b] + P_{masks[v]} n[b], 0, 1) ([V * B][3][H][W], the layout of ica_transfer_apply) and, if asked for,
+ * mse_in [V][B] = mean((out[v * B + b] - im_s[b])^2).  out == NULL (then mse_in == NULL, masks unused): the energies
+ * only.  The variants go through the kernel ica_band_split_chunk() at a time, the forward DCT once per chunk.
+ * ica_band_project: y = P_mask x; mask 0 writes zeros.
+ * ica_band_prologue / ica_band_adam: the step kernels of the band-limited L2 attack, ica_attack_prologue_ex and
+ * ica_attack_adam_ex at clamp_in = 1 with p = P_mask(clip(noise, +-eps)) in place of clip(noise, +-eps):
+ *   prologue  im_in = clamp(im_s + p, 0, 1) -> im_in4 [B][H][W][4] nChw4c (lane 3 = 0);
+ *             loss_i [B] = mean((im_s - im_in)^2)
+ *   adam      g = loss_i[b] > thr ? -2 fl(invN (im_s - im_in)) : gnet4 (nChw4c; row gpos[b] if gpos, else b; lane 3 is
+ *             never used); g = bound-backward at im_s + p against [0, 1]; g = P_mask g; g = bound-backward at the noise
+ *             against +-eps; torch's Adam step on noise, m, v in place.  branch[b] = cheap, census[b] += cheap,
+ *             im_in_out = im_in: each optional. */
+int ica_band_split_chunk(void);
+int ica_band_max_variants(void);
+size_t ica_band_split_ws_size(int V, int B, int H, int W);
+int ica_band_split(const float* im_s, const float* im_adv, const int* masks, int V, int B, int H, int W, float* out,
+                   float* energy, float* mse_in, float* ws, hipStream_t stream);
+int ica_band_project(const float* x, int mask, int B, int H, int W, float* y, hipStream_t stream);
+size_t ica_band_prologue_ws_size(int B, int H, int W);
+int ica_band_prologue(const float* noise, const float* im_s, float* im_in4, float* loss_i, int B, int H, int W,
+                      float eps, int mask, float* ws, hipStream_t stream);
+int ica_band_adam(float* noise, const float* im_s, const float* gnet4, const float* loss_i, float* m, float* v,
+                  float* im_in_out, int B, int H, int W, float eps, float thr, float invN, float bc2s, float neg_step,
+                  int* branch, const int* gpos, int* census, int mask, hipStream_t stream);
+
 /* ---- iterated re-compression (ica_recompress.hip) ---------------------------
  * The step between two generations of recompression.py (coder.py:21-48), on the device and for a whole batch.
  * Images are B x 3 x H x W; codes are one uint32 per pixel, r | g << 8 | b << 16, [B][H][W] (the top byte is written
